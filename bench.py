@@ -1,8 +1,13 @@
 """Headline benchmark: documents/sec through the full language-ID + Gopher + C4 (+FineWeb)
 pipeline (BASELINE.json metric) on N MI355X GPUs of one node, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 is launched by torch.distributed.run; ranks read RANK/LOCAL_RANK/WORLD_SIZE)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (ms_per_step = the
+wall milliseconds of one timed step). --dump-outputs DIR also writes the last timed step's
+result as .npy arrays: the inputs are seeded, so two builds run with the same arguments can be
+compared output for output. --full is where measurements that need runs of their own belong.
 
 One step = every rank pushes one batch of synthetic CommonCrawl-shaped documents (log-normal
 lengths around 1 KB, 5 languages) through the whole pipeline: H2D staging, all device stages
@@ -47,6 +52,74 @@ def cpu_baseline(config_path: str, mean_bytes: int):
     return float(e["docs_per_sec"])
 
 
+DUMP_MAX_DOCS = 1 << 19        # --dump-outputs: documents with per-document columns (all, up to this many)
+DUMP_SAMPLE_DOCS = 4096        # ... documents whose output bytes are written in full
+DUMP_SAMPLE_BYTES = 3 << 20    # ... up to this many text / metadata bytes (float32: 4 B per byte)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir: str, res, prefix: str = "") -> None:
+    """--dump-outputs: what the last timed step handed to its caller (a BatchResult), as .npy
+    arrays keyed by input row, so that they do not depend on how the output parts were split.
+
+    rows (float64): the input rows described, all of them unless the batch has more than
+    DUMP_MAX_DOCS (then a seeded sample, ascending). Per such row: status and fail_step (float32),
+    and for its entry in the kept / excluded output the byte length and CRC-32 of the text and of
+    the metadata JSON (float64; -1 = none: an error row, null metadata). sample_rows: a seeded
+    sample of rows whose output text and metadata bytes are written out (float32) with their
+    offsets (float64; the first len(offsets) - 1 sample rows, whole documents under the byte cap).
+    Under 64 MB in all."""
+    import zlib
+
+    n = res.n_docs
+    rng = np.random.default_rng(DUMP_SEED)
+    docs = np.arange(n) if n <= DUMP_MAX_DOCS else np.sort(rng.choice(n, size=DUMP_MAX_DOCS, replace=False))
+    sample = np.sort(rng.choice(docs, size=min(len(docs), DUMP_SAMPLE_DOCS), replace=False))
+    pos = np.full(n, -1, dtype=np.int64)
+    pos[docs] = np.arange(len(docs))
+    slot = np.full(n, -1, dtype=np.int64)
+    slot[sample] = np.arange(len(sample))
+    tl, tc, ml, mc = (np.full(len(docs), -1.0, dtype=np.float64) for _ in range(4))
+    s_text = [b""] * len(sample)
+    s_meta = [b""] * len(sample)
+    for part in list(res.kept) + list(res.excluded):
+        td = memoryview(np.ascontiguousarray(part.text_data))
+        md = memoryview(np.ascontiguousarray(part.meta_data))
+        to, mo = np.asarray(part.text_off).tolist(), np.asarray(part.meta_off).tolist()
+        mv = np.asarray(part.meta_valid).tolist()
+        rows = np.asarray(part.rows)
+        for i in np.nonzero(pos[rows] >= 0)[0].tolist():
+            r = int(rows[i])
+            t = td[to[i]:to[i + 1]]
+            m = md[mo[i]:mo[i + 1]] if mv[i] else None
+            k = pos[r]
+            tl[k], tc[k] = len(t), zlib.crc32(t)
+            if m is not None:
+                ml[k], mc[k] = len(m), zlib.crc32(m)
+            if slot[r] >= 0:
+                s_text[slot[r]] = bytes(t)
+                s_meta[slot[r]] = bytes(m) if m is not None else b""
+
+    def packed(chunks):
+        off = np.zeros(len(chunks) + 1, dtype=np.int64)
+        np.cumsum([len(c) for c in chunks], out=off[1:])
+        keep = int(np.searchsorted(off, DUMP_SAMPLE_BYTES, side="right")) - 1
+        data = np.frombuffer(b"".join(chunks[:keep]), dtype=np.uint8).astype(np.float32)
+        return data, off[:keep + 1].astype(np.float64)
+
+    arrays = {"rows": docs.astype(np.float64),
+              "status": np.asarray(res.status)[docs].astype(np.float32),
+              "fail_step": np.asarray(res.fail_step)[docs].astype(np.float32),
+              "text_len": tl, "text_crc32": tc, "meta_len": ml, "meta_crc32": mc,
+              "sample_rows": sample.astype(np.float64)}
+    arrays["sample_text"], arrays["sample_text_off"] = packed(s_text)
+    arrays["sample_meta"], arrays["sample_meta_off"] = packed(s_meta)
+    assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -77,6 +150,13 @@ def main():
     ap.add_argument("--ar1-every", type=int, default=1,
                     help="all-reduce the counter vector every N steps (0: only the final totals)")
     ap.add_argument("--ar1-window", type=int, default=4, help="outstanding async all-reduces before a wait")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (see "
+                         "dump_outputs; ranks above 0 prefix their files with rank<r>_)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that need runs of their own. There are none today: "
+                         "vs_baseline is a table lookup and every other figure on the result line is a "
+                         "by-product of the timed steps, so a plain run and a --full run do the same work")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.docs_per_step < 1 or args.gpus < 1:
         ap.error("--steps must be >= 1, --warmup >= 0, --docs-per-step >= 1 and --gpus >= 1")
@@ -209,6 +289,8 @@ def main():
     value = docs_total / elapsed_max
     lid = getattr(eng, "langid", None)
     base = cpu_baseline(args.config, args.mean_bytes) if args.vocab == "small" and not args.mixed_script else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, prefix=f"rank{rank}_" if rank else "")
     if rank == 0:
         line = {
             "metric": METRIC,

@@ -1,11 +1,13 @@
 """bench.py output contract (one JSON line from rank 0 with the driver's keys) on the CPU backend:
 one process, and two gloo ranks under torch.distributed.run (global batch = per-rank batch x
-world, counters summed over ranks, value = global docs / max-over-ranks seconds)."""
+world, counters summed over ranks, value = global docs / max-over-ranks seconds); --full and
+--dump-outputs (reproducible .npy dump of the last timed step's result)."""
 import json
 import os
 import socket
 import subprocess
 import sys
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--backend", "cpu", "--segmentation", "rules", "--docs-per-step", "128", "--pool", "64",
@@ -50,6 +52,43 @@ def _check(line, steps, warmup, world):
 def test_bench_single_process_contract():
     line = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1"] + ARGS)
     _check(line, 2, 1, 1)
+
+
+def test_bench_full_option_keeps_the_contract():
+    """--full (where measurements with runs of their own go) prints the same single line."""
+    line = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "0", "--full"] + ARGS)
+    _check(line, 3, 0, 1)
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's result as float .npy arrays that agree with the
+    line's counters and are identical from run to run (seeded inputs)."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        line = _run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path / d)] + ARGS)
+        _check(line, 1, 1, 1)
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert set(a) == set(b) >= {"rows", "status", "fail_step", "text_len", "text_crc32", "meta_len", "meta_crc32",
+                                "sample_rows", "sample_text", "sample_text_off", "sample_meta", "sample_meta_off"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    # one timed step: the dumped per-document columns are that step's counters
+    assert np.array_equal(a["rows"], np.arange(128))
+    assert int((a["status"] == 0).sum()) == line["kept"] and int((a["status"] == 1).sum()) == line["excluded"]
+    assert np.array_equal(a["fail_step"] < 0, a["status"] == 0)
+    assert (a["text_len"][a["status"] < 2] >= 0).all()
+    # the sampled bytes are the documents the per-document columns describe
+    off = a["sample_text_off"].astype(np.int64)
+    rows = a["sample_rows"].astype(np.int64)[:len(off) - 1]
+    assert np.array_equal(np.diff(off), a["text_len"][rows]) and off[-1] == len(a["sample_text"])
+    r0 = int(rows[0])
+    assert zlib.crc32(a["sample_text"][off[0]:off[1]].astype(np.uint8).tobytes()) == a["text_crc32"][r0]
 
 
 def test_bench_two_ranks_contract():
