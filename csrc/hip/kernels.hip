@@ -11,6 +11,12 @@
 //  tb_langid_mfma     : fastText int8 embedding bag + bf16 MFMA head (16 docs per tile) -> language records
 //  tb_c4_pass_a       : C4 line filtering, citation removal, rewritten text into scratch
 //  tb_c4_pass_b       : compaction of the rewritten texts into the next content version
+//
+// Launch ABI (the extern "C" block at the end): the argument groups every document kernel shares
+// travel as `const T*` to plain structs -- TbTables (Unicode tables, hash powers: per batch),
+// TbDocs (content version, launch positions, counts, dead marks: per launch), TbWork (scratch,
+// records, flags, LDS slice: per launch), DictIn / DictLines (devplan.h) -- and the launchers
+// unpack them into the kernels' argument lists. ops/kernels.py holds the one ctypes mirror of each.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -1733,24 +1739,70 @@ extern "C" {
 
 int tb_scan_strided_i64(hipStream_t stream, const int64_t* src, int64_t stride, int64_t n, int64_t* out);  // runtime.hip
 
-int tb_stage_analyze(hipStream_t stream, const void* plan, const void* stage, const uint8_t* bytes,
-                     const int64_t* off, const int32_t* perm, int32_t ndocs, char* scratch,
-                     const int64_t* scratch_off, const uint64_t* pw, uint32_t pw_n, const uint16_t* s1,
-                     const uint32_t* s2, const uint16_t* l1, const int32_t* l2, int64_t* rec, uint32_t* flags,
-                     uint32_t lds_bytes, uint64_t* prof, int32_t waves, int32_t nblocks, const uint8_t* dead,
-                     uint32_t* line_stats, void* gr_export, const int64_t* dict_moff, const uint32_t* dict_bits,
-                     const uint32_t* dict_words) {
-  if (ndocs <= 0) return 0;
-  if (nblocks <= 0) nblocks = ndocs;  // grid: docs perm[0 .. nblocks)
+// Launch arguments travel in a few plain structs (mirrored field by field as ctypes.Structure in
+// ops/kernels.py, sizes checked through tb_sizeof_*); each launcher unpacks the fields it needs
+// into its kernel's argument list. DictIn / DictLines (devplan.h) are passed the same way.
+struct TbTables {      // read-only tables of a batch
+  DevTables ucd;       // Unicode property tables (s1, s2, l1, l2)
+  const uint64_t* pw;  // B^0 .. B^pw_n, then B^-0 .. B^-pw_n (hashes)
+  uint32_t pw_n;
+};
+struct TbDocs {          // the documents of one launch
+  const uint8_t* bytes;  // a content version: text and offsets [ndocs + 1]
+  const int64_t* off;
+  const int32_t* perm;      // launch positions perm[0 .. n_launch)
+  const uint8_t* dead;      // the batch's dead marks, or null
+  int32_t n_launch, ndocs;  // ndocs: documents in the batch (the record stride)
+};
+struct TbWork {  // what a document kernel writes
+  char* scratch;
+  const int64_t* scratch_off;  // slices by launch position
+  int64_t* rec;
+  uint32_t* flags;
+  uint64_t* prof;      // phase counters, or null
+  uint32_t lds_bytes;  // dynamic LDS slice per workgroup
+};
+struct TbBadWords {  // inputs of one C4BadWords step (tb_badwords_match)
+  const int32_t* root;
+  const uint8_t* cjk;
+  const uint32_t* table;
+  const uint16_t* f1;
+  const int32_t *f2, *seg_doc, *seg_idx;
+  int32_t root0, cjk0;
+  uint32_t dead_max, table_mask, seg_bytes;
+};
+struct TbResolveOut {  // outputs and scratch of tb_resolve
+  int32_t* fail;
+  uint8_t *status, *fver;
+  int64_t *lanes, *sc;
+  uint8_t* out;
+  int64_t cap;  // bytes of out
+  int64_t* out_off;
+  int32_t *rows, *err;
+};
+
+size_t tb_sizeof_tables() { return sizeof(TbTables); }
+size_t tb_sizeof_docs() { return sizeof(TbDocs); }
+size_t tb_sizeof_work() { return sizeof(TbWork); }
+size_t tb_sizeof_badwords() { return sizeof(TbBadWords); }
+size_t tb_sizeof_resolve_out() { return sizeof(TbResolveOut); }
+size_t tb_sizeof_dict_in() { return sizeof(DictIn); }
+size_t tb_sizeof_dict_lines() { return sizeof(DictLines); }
+
+// Wave kernels: grid = launch positions perm[0 .. n_launch) (n_launch <= 0: all ndocs).
+int tb_stage_analyze(hipStream_t stream, const void* plan, const void* stage, const TbDocs* d, const TbWork* w,
+                     const TbTables* tb, uint32_t* line_stats, void* gr_export, const DictIn* dict) {
+  const uint32_t lds_bytes = w->lds_bytes;
+  if (d->ndocs <= 0) return 0;
+  const int32_t nblocks = d->n_launch <= 0 ? d->ndocs : d->n_launch;
   if (lds_bytes > kMaxLdsPerDoc) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
-  if (waves != TB_STAGE_WPE) return (int)hipErrorInvalidValue;  // the one build (see TB_STAGE_KERNEL)
-  auto kern = k_stage_analyze_wave;
+  auto kern = k_stage_analyze_wave;  // the one build (see TB_STAGE_KERNEL)
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds_bytes, stream, (const DevPlan*)plan,
-                     (const DevStage*)stage, bytes, off, perm, ndocs, scratch, scratch_off, pw, pw_n, t, rec, flags,
-                     lds_bytes, prof, dead, line_stats, (GrExport*)gr_export, DictIn{dict_moff, dict_bits, dict_words});
+                     (const DevStage*)stage, d->bytes, d->off, d->perm, d->ndocs, w->scratch, w->scratch_off, tb->pw,
+                     tb->pw_n, tb->ucd, w->rec, w->flags, lds_bytes, w->prof, d->dead, line_stats, (GrExport*)gr_export,
+                     dict ? *dict : DictIn{});
   return (int)hipGetLastError();
 }
 
@@ -1760,15 +1812,20 @@ int tb_stage_analyze(hipStream_t stream, const void* plan, const void* stage, co
 // with block != 0 one workgroup per document (k_gr_ngrams<256>); block == 0: k_gr_split_wave for
 // all. Measured (profiles/r7_ngram): workgroups of the 512-word class lost to the per-order waves
 // for documents over 1.2 KB (LDS-limited occupancy), all-waves lost to this split.
-int tb_gr_split_wave(hipStream_t stream, const void* stage, int32_t gr_step, const int32_t* perm, int32_t n_docs,
-                     int32_t n_tasks, int32_t ndocs, const void* gr_export, const uint64_t* pw, uint32_t pw_n,
-                     const uint16_t* s1, const uint32_t* s2, const uint16_t* l1, const int32_t* l2, int64_t* rec,
-                     uint32_t* flags, uint32_t lds_bytes, int32_t block, uint64_t* prof, int32_t n_big) {
+int tb_gr_split_wave(hipStream_t stream, const void* stage, int32_t gr_step, const TbDocs* d, int32_t n_tasks,
+                     const void* gr_export, const TbWork* w, const TbTables* tb, int32_t block, int32_t n_big) {
+  const int32_t* perm = d->perm;
+  const int32_t n_docs = d->n_launch, ndocs = d->ndocs;
+  const DevTables& t = tb->ucd;
+  const uint64_t* pw = tb->pw;
+  const uint32_t pw_n = tb->pw_n, lds_bytes = w->lds_bytes;
+  int64_t* rec = w->rec;
+  uint32_t* flags = w->flags;
+  uint64_t* prof = w->prof;
   if (n_docs <= 0 || n_tasks <= 0) return 0;
   if (!perm || !gr_export || gr_step < 0 || gr_step >= kMaxStageSteps || n_tasks > 2 * kMaxNgramEntries ||
       lds_bytes > kMaxLdsPerDoc || n_big < 0 || n_big > n_docs)
     return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
   const GrExport* ex = (const GrExport*)gr_export;
   const int32_t n_wave = block ? n_big : n_docs;
   if (n_wave > 0) {
@@ -1794,42 +1851,37 @@ int tb_gr_split_wave(hipStream_t stream, const void* stage, int32_t gr_step, con
 }
 
 // Long-document variants: `perm` must point at the long prefix of the length-sorted
-// permutation, `nblocks` documents, one workgroup each.
-int tb_stage_analyze_blk(hipStream_t stream, const void* plan, const void* stage, const uint8_t* bytes,
-                         const int64_t* off, const int32_t* perm, int32_t nblocks, int32_t ndocs, char* scratch,
-                         const int64_t* scratch_off, const uint64_t* pw, uint32_t pw_n, const uint16_t* s1,
-                         const uint32_t* s2, const uint16_t* l1, const int32_t* l2, int64_t* rec, uint32_t* flags,
-                         uint32_t lds_bytes, uint64_t* prof, const uint8_t* dead, void* gr_export, int32_t n_split,
-                         uint32_t split_bytes, int32_t threads, uint32_t* line_stats, const void* pre,
-                         int32_t n_pre, const int64_t* dict_moff, const uint32_t* dict_bits, const uint32_t* dict_words) {
+// permutation, `n_launch` documents, one workgroup each. `pre`: the pre-pass descriptors of
+// every launched document (k_stage_analyze_blk_pre), or null.
+int tb_stage_analyze_blk(hipStream_t stream, const void* plan, const void* stage, const TbDocs* d, const TbWork* w,
+                         const TbTables* tb, void* gr_export, int32_t n_split, uint32_t split_bytes,
+                         uint32_t* line_stats, const void* pre, const DictIn* dict) {
+  const int32_t nblocks = d->n_launch;
+  const uint32_t lds_bytes = w->lds_bytes;
   if (nblocks <= 0) return 0;
-  if (!perm || lds_bytes > kMaxLdsPerBlk || n_split < 0 || n_split > nblocks) return (int)hipErrorInvalidValue;
-  if (threads != kBlockThreads) return (int)hipErrorInvalidValue;
-  if (pre && (threads != kBlockThreads || n_pre != nblocks)) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
+  if (!d->perm || lds_bytes > kMaxLdsPerBlk || n_split < 0 || n_split > nblocks) return (int)hipErrorInvalidValue;
   auto kern = pre ? k_stage_analyze_blk_pre : k_stage_analyze_blk;
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds_bytes, stream,
-                     (const DevPlan*)plan, (const DevStage*)stage, bytes, off, perm, ndocs, scratch, scratch_off, pw,
-                     pw_n, t, rec, flags, lds_bytes, prof, dead, (GrExport*)gr_export, n_split,
-                     split_bytes, line_stats, (const PreDoc*)pre, n_pre, DictIn{dict_moff, dict_bits, dict_words});
+  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kBlockThreads), lds_bytes, stream, (const DevPlan*)plan,
+                     (const DevStage*)stage, d->bytes, d->off, d->perm, d->ndocs, w->scratch, w->scratch_off, tb->pw,
+                     tb->pw_n, tb->ucd, w->rec, w->flags, lds_bytes, w->prof, d->dead, (GrExport*)gr_export, n_split,
+                     split_bytes, line_stats, (const PreDoc*)pre, pre ? nblocks : 0, dict ? *dict : DictIn{});
   return (int)hipGetLastError();
 }
 
 // gr_export: n_split descriptors written by tb_stage_analyze_blk (zeroed by the caller first);
 // gr_step: index of the GopherRepetition step in the stage, n_tasks its duplicated + top n-gram
 // orders.
-int tb_gr_dup_split(hipStream_t stream, const void* stage, int32_t gr_step, const int32_t* perm, int32_t n_split,
-                    int32_t n_tasks, int32_t ndocs, const void* gr_export, const uint64_t* pw, uint32_t pw_n,
-                    const uint16_t* s1, const uint32_t* s2, const uint16_t* l1, const int32_t* l2, int64_t* rec,
-                    uint32_t* flags, uint32_t lds_bytes, uint32_t* cursor) {
+int tb_gr_dup_split(hipStream_t stream, const void* stage, int32_t gr_step, const TbDocs* d, int32_t n_tasks,
+                    const void* gr_export, const TbWork* w, const TbTables* tb, uint32_t* cursor) {
+  const int32_t n_split = d->n_launch;
+  const uint32_t lds_bytes = w->lds_bytes;
   if (n_split <= 0 || n_tasks <= 0) return 0;
-  if (!perm || !gr_export || gr_step < 0 || gr_step >= kMaxStageSteps || n_tasks > 2 * kMaxNgramEntries + 2 ||
+  if (!d->perm || !gr_export || gr_step < 0 || gr_step >= kMaxStageSteps || n_tasks > 2 * kMaxNgramEntries + 2 ||
       lds_bytes > kMaxLdsPerBlk)
     return (int)hipErrorInvalidValue;
   if (!cursor) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)k_gr_dup_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   // the persistent grid: resident workgroups per CU (registers, LDS) x CUs, at most one per task
@@ -1844,17 +1896,22 @@ int tb_gr_dup_split(hipStream_t stream, const void* stage, int32_t gr_step, cons
   const int grid = (int)std::min<int64_t>(total, (int64_t)cus * per_cu);
   (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t), stream);
   hipLaunchKernelGGL(k_gr_dup_split, dim3((uint32_t)grid), dim3(kBlockThreads), lds_bytes, stream,
-                     (const DevStage*)stage, gr_step, perm, n_split, n_tasks, ndocs, (const GrExport*)gr_export, pw,
-                     pw_n, t, rec, flags, lds_bytes, cursor);
+                     (const DevStage*)stage, gr_step, d->perm, n_split, n_tasks, d->ndocs, (const GrExport*)gr_export,
+                     tb->pw, tb->pw_n, tb->ucd, w->rec, w->flags, lds_bytes, cursor);
   return (int)hipGetLastError();
 }
 
 // GopherRepetition word arrays of the npre pre-pass documents (after tb_pre_decode; the
 // descriptors' wh / wtab / wk / wpb / wcsum / wslot / wid / wl hold [W + 1]-sized buffers,
 // wtab [1.5 W + 2], wcsum [4 chunks]; chunks_max >= ceil(max W / 2048)).
-int tb_pre_wcanon(hipStream_t stream, const uint8_t* bytes, const int64_t* off, const int32_t* perm, int32_t npre,
-                  const uint8_t* dead, void* pre, uint32_t chunks_max, const uint64_t* pw, uint32_t pw_n,
+int tb_pre_wcanon(hipStream_t stream, const TbDocs* d, void* pre, uint32_t chunks_max, const TbTables* tb,
                   uint32_t* flags) {
+  const uint8_t *bytes = d->bytes, *dead = d->dead;
+  const int64_t* off = d->off;
+  const int32_t* perm = d->perm;
+  const int32_t npre = d->n_launch;
+  const uint64_t* pw = tb->pw;
+  const uint32_t pw_n = tb->pw_n;
   if (npre <= 0) return 0;
   if (!perm || !pre || !pw || !flags || chunks_max == 0 || npre > 65535) return (int)hipErrorInvalidValue;
   const PreDoc* p = (const PreDoc*)pre;
@@ -1874,17 +1931,19 @@ size_t tb_sizeof_pre_doc() { return sizeof(PreDoc); }
 // Decode + word-break marks of the first npre launch positions of the long-document launch
 // (`pre`: npre descriptors with n / off / prop / wbm set, C and dict zeroed; cnt: int64
 // [npre * tiles_max], tiles_max >= ceil(max n / 16 KB)).
-int tb_pre_decode(hipStream_t stream, const uint8_t* bytes, const int64_t* off, const int32_t* perm, int32_t npre,
-                  const uint8_t* dead, void* pre, uint32_t tiles_max, int64_t* cnt, const uint16_t* s1,
-                  const uint32_t* s2, const uint16_t* l1, const int32_t* l2) {
+int tb_pre_decode(hipStream_t stream, const TbDocs* d, void* pre, uint32_t tiles_max, int64_t* cnt,
+                  const TbTables* tb) {
+  const uint8_t *bytes = d->bytes, *dead = d->dead;
+  const int64_t* off = d->off;
+  const int32_t* perm = d->perm;
+  const int32_t npre = d->n_launch;
   if (npre <= 0) return 0;
   if (!perm || !pre || !cnt || tiles_max == 0 || npre > 65535) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
   const dim3 g(tiles_max, (uint32_t)npre);
   hipLaunchKernelGGL(k_pre_count, g, dim3(kPreThreads), 0, stream, bytes, off, perm, dead, (const PreDoc*)pre,
                      tiles_max, cnt);
   hipLaunchKernelGGL(k_pre_decode, g, dim3(kPreThreads), 0, stream, bytes, off, perm, dead, (PreDoc*)pre, tiles_max,
-                     (const int64_t*)cnt, t);
+                     (const int64_t*)cnt, tb->ucd);
   // chunks of 64 code points: C + 1 <= n + 1 positions
   const uint32_t chunks = tiles_max * (kPreTile / 64) + 1;
   hipLaunchKernelGGL(k_pre_wb, dim3(chunks, (uint32_t)npre), dim3(64), 0, stream, perm, dead, (PreDoc*)pre);
@@ -1897,40 +1956,35 @@ int tb_pre_decode(hipStream_t stream, const uint8_t* bytes, const int64_t* off, 
   return (int)hipGetLastError();
 }
 
-int tb_c4_pass_a_blk(hipStream_t stream, const void* c4, const uint8_t* bytes, const int64_t* off,
-                     const int32_t* perm, int32_t nblocks, int32_t ndocs, char* scratch, const int64_t* scratch_off,
-                     const uint64_t* pw, uint32_t pw_n, const uint16_t* s1, const uint32_t* s2, const uint16_t* l1,
-                     const int32_t* l2, int64_t* rec, int64_t* src, uint32_t* flags, uint32_t lds_bytes,
-                     uint64_t* prof, const uint8_t* dead, const uint32_t* line_stats, uint32_t* c4_words,
-                     const int64_t* dict_loff, const uint32_t* dict_ldata) {
+int tb_c4_pass_a_blk(hipStream_t stream, const void* c4, const TbDocs* d, const TbWork* w, const TbTables* tb,
+                     int64_t* src, const uint32_t* line_stats, uint32_t* c4_words, const DictLines* dict) {
+  const int32_t nblocks = d->n_launch;
+  const uint32_t lds_bytes = w->lds_bytes;
   if (nblocks <= 0) return 0;
-  if (!perm || lds_bytes > kMaxLdsPerBlk) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
+  if (!d->perm || lds_bytes > kMaxLdsPerBlk) return (int)hipErrorInvalidValue;
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)k_c4_pass_a_blk, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_bytes);
   hipLaunchKernelGGL(k_c4_pass_a_blk, dim3(nblocks), dim3(kBlockThreads), lds_bytes, stream, (const DevC4*)c4,
-                     bytes, off, perm, ndocs, scratch, scratch_off, pw, pw_n, t, rec, src, flags, lds_bytes, prof, dead,
-                     line_stats, c4_words, DictLines{dict_loff, dict_ldata});
+                     d->bytes, d->off, d->perm, d->ndocs, w->scratch, w->scratch_off, tb->pw, tb->pw_n, tb->ucd, w->rec,
+                     src, w->flags, lds_bytes, w->prof, d->dead, line_stats, c4_words, dict ? *dict : DictLines{});
   return (int)hipGetLastError();
 }
 
 int tb_block_threads() { return kBlockThreads; }
 
-int tb_badwords_match(hipStream_t stream, const uint8_t* bytes, const int64_t* off, int32_t nitems, const int32_t* root,
-                      const uint8_t* cjk, int32_t root0, int32_t cjk0, const uint8_t* dead, uint32_t dead_max,
-                      const uint32_t* table, uint32_t table_mask, const uint16_t* s1, const uint32_t* s2,
-                      const uint16_t* l1, const int32_t* l2, const uint16_t* f1, const int32_t* f2, int8_t* matched,
-                      const int32_t* seg_doc, const int32_t* seg_idx, uint32_t seg_bytes) {
+// n_launch items: the documents [0, n_launch), or with seg_doc / seg_idx that many segments.
+int tb_badwords_match(hipStream_t stream, const TbDocs* d, const TbTables* tb, const TbBadWords* b, int8_t* matched) {
+  const int32_t nitems = d->n_launch;
   if (nitems <= 0) return 0;
-  if (!table || ((table_mask + 1) & table_mask) != 0 || seg_bytes < 256 || (seg_bytes & 255) || (!seg_doc != !seg_idx))
+  if (!b->table || ((b->table_mask + 1) & b->table_mask) != 0 || b->seg_bytes < 256 || (b->seg_bytes & 255) ||
+      (!b->seg_doc != !b->seg_idx))
     return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
-  const BwTable bt{table, table_mask};
-  const BwFold fold{f1, f2};
-  hipLaunchKernelGGL(k_badwords_match, dim3((nitems + kBwWaves - 1) / kBwWaves), dim3(64 * kBwWaves), 0, stream, bytes,
-                     off, nitems, root, cjk, root0, cjk0, dead, dead_max, bt, t, fold, matched, seg_doc, seg_idx,
-                     seg_bytes);
+  const BwTable bt{b->table, b->table_mask};
+  const BwFold fold{b->f1, b->f2};
+  hipLaunchKernelGGL(k_badwords_match, dim3((nitems + kBwWaves - 1) / kBwWaves), dim3(64 * kBwWaves), 0, stream,
+                     d->bytes, d->off, nitems, b->root, b->cjk, b->root0, b->cjk0, d->dead, b->dead_max, bt, tb->ucd,
+                     fold, matched, b->seg_doc, b->seg_idx, b->seg_bytes);
   return (int)hipGetLastError();
 }
 
@@ -1946,36 +2000,31 @@ int tb_langid_prepare(hipStream_t stream, const uint8_t* E, uint8_t* aux) {
 // k_langid_mfma: records of every document (perm order, 16 per tile); Eb = E + 128 as uint8
 // [buckets * 16] (the biased block-sparse embedding table), aux its pair table
 // (tb_langid_prepare), WT bf16 bits [16 * 32] (the head transposed, columns >= 5 zero), bias float [8].
-int tb_langid_mfma(hipStream_t stream, const uint8_t* bytes, const int64_t* off, const int32_t* perm, int32_t ndocs,
-                   const uint16_t* s1, const uint32_t* s2, const uint16_t* l1, const int32_t* l2, const uint8_t* E,
-                   const uint8_t* aux, const uint16_t* WT, double w_scale, const float* bias, int64_t* rec,
-                   int32_t width, uint64_t* prof) {
+int tb_langid_mfma(hipStream_t stream, const TbDocs* d, const TbTables* tb, const uint8_t* E, const uint8_t* aux,
+                   const uint16_t* WT, double w_scale, const float* bias, int64_t* rec, int32_t width,
+                   uint64_t* prof) {
+  const int32_t ndocs = d->n_launch;
   if (ndocs <= 0) return 0;
   if (!E || !aux || !WT || !bias || !rec || width < 2 || !(w_scale > 0)) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
   const int ntiles = (ndocs + kLidTile - 1) / kLidTile;
   const int cus = device_cus();
   const int grid = ntiles < 4 * cus ? ntiles : 4 * cus;
-  hipLaunchKernelGGL(k_langid_mfma, dim3(grid), dim3(64 * kLidWaves), 0, stream, bytes, off, perm, ndocs, t, E, aux,
-                     WT, w_scale, bias, rec, width, prof);
+  hipLaunchKernelGGL(k_langid_mfma, dim3(grid), dim3(64 * kLidWaves), 0, stream, d->bytes, d->off, d->perm, ndocs,
+                     tb->ucd, E, aux, WT, w_scale, bias, rec, width, prof);
   return (int)hipGetLastError();
 }
 
-int tb_c4_pass_a(hipStream_t stream, const void* c4, const uint8_t* bytes, const int64_t* off, const int32_t* perm,
-                 int32_t ndocs, char* scratch, const int64_t* scratch_off, const uint64_t* pw, uint32_t pw_n,
-                 const uint16_t* s1, const uint32_t* s2, const uint16_t* l1, const int32_t* l2, int64_t* rec,
-                 int64_t* src, uint32_t* flags, uint32_t lds_bytes, uint64_t* prof, int32_t nblocks,
-                 const uint8_t* dead, const uint32_t* line_stats, uint32_t* c4_words, const int64_t* dict_loff,
-                 const uint32_t* dict_ldata) {
-  if (ndocs <= 0) return 0;
-  if (nblocks <= 0) nblocks = ndocs;
+int tb_c4_pass_a(hipStream_t stream, const void* c4, const TbDocs* d, const TbWork* w, const TbTables* tb,
+                 int64_t* src, const uint32_t* line_stats, uint32_t* c4_words, const DictLines* dict) {
+  const uint32_t lds_bytes = w->lds_bytes;
+  if (d->ndocs <= 0) return 0;
+  const int32_t nblocks = d->n_launch <= 0 ? d->ndocs : d->n_launch;
   if (lds_bytes > kMaxLdsPerDoc) return (int)hipErrorInvalidValue;
-  DevTables t{s1, s2, l1, l2};
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)k_c4_pass_a, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipLaunchKernelGGL(k_c4_pass_a, dim3(nblocks), dim3(64), lds_bytes, stream, (const DevC4*)c4, bytes, off, perm, ndocs,
-                     scratch, scratch_off, pw, pw_n, t, rec, src, flags, lds_bytes, prof, dead, line_stats, c4_words,
-                     DictLines{dict_loff, dict_ldata});
+  hipLaunchKernelGGL(k_c4_pass_a, dim3(nblocks), dim3(64), lds_bytes, stream, (const DevC4*)c4, d->bytes, d->off,
+                     d->perm, d->ndocs, w->scratch, w->scratch_off, tb->pw, tb->pw_n, tb->ucd, w->rec, src, w->flags,
+                     lds_bytes, w->prof, d->dead, line_stats, c4_words, dict ? *dict : DictLines{});
   return (int)hipGetLastError();
 }
 
@@ -2007,8 +2056,11 @@ size_t tb_sizeof_gate() { return sizeof(DevGate); }
 // the end sets *err and is not written), out_off ndocs+1, rows ndocs.
 int tb_resolve(hipStream_t stream, const void* rp, const int64_t* const* recs, int32_t nrecs, int32_t ndocs,
                const uint32_t* flags, const uint8_t* const* vb, const int64_t* const* vo, int32_t nver,
-               int32_t* fail, uint8_t* status, uint8_t* fver, int64_t* lanes, int64_t* sc, uint8_t* out,
-               int64_t cap, int64_t* out_off, int32_t* rows, int32_t* err) {
+               const TbResolveOut* o) {
+  int32_t *fail = o->fail, *rows = o->rows, *err = o->err;
+  uint8_t *status = o->status, *fver = o->fver, *out = o->out;
+  int64_t *lanes = o->lanes, *sc = o->sc, *out_off = o->out_off;
+  const int64_t cap = o->cap;
   if (ndocs <= 0) return 0;
   if (nrecs < 0 || nrecs > kMaxGateSteps || nver < 1 || nver > kMaxVersions) return (int)hipErrorInvalidValue;
   GateRecs r{};
@@ -2046,7 +2098,7 @@ int tb_pow_table(hipStream_t stream, uint64_t* pw, uint32_t n) {
 int tb_phase_slots() { return kPhaseSlots; }
 int tb_stage_waves() { return TB_STAGE_WPE; }  // waves per SIMD the wave stage kernel is built for
 
-int tb_abi_version() { return 24; }
+int tb_abi_version() { return 25; }
 size_t tb_sizeof_plan() { return sizeof(DevPlan); }
 size_t tb_sizeof_stage() { return sizeof(DevStage); }
 size_t tb_sizeof_c4() { return sizeof(DevC4); }

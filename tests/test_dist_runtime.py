@@ -185,17 +185,16 @@ def test_block_kernels_reject_oversized_lds_slice():
     lib = native.hip()
     kernels.declare(lib)
     dummy = ctypes.c_void_p(16)
+    tables = kernels.Tables(16, 16, 16, 16, 16, 0)
+    docs = kernels.Docs(16, 16, 16, None, 1, 1)
     for lds, want_err in ((160 * 1024, True), (128 * 1024 + 16, True)):
         # (every launcher here returns before any HIP call when the slice is too large)
-        rc = lib.tb_stage_analyze_blk(None, dummy, dummy, dummy, dummy, dummy, 1, 1, dummy, dummy, dummy, 0,
-                                      dummy, dummy, dummy, dummy, dummy, dummy, lds, None, None, None, 0, 0, 512, None, None, 0,
-                                      None, None, None)
+        work = kernels.Work(16, 16, 16, 16, None, lds)
+        rc = lib.tb_stage_analyze_blk(None, dummy, dummy, docs, work, tables, None, 0, 0, None, None, None)
         assert (rc != 0) == want_err
-        rc = lib.tb_gr_dup_split(None, dummy, 0, dummy, 1, 6, 1, dummy, dummy, 0, dummy, dummy, dummy, dummy,
-                                 dummy, dummy, lds, dummy)
+        rc = lib.tb_gr_dup_split(None, dummy, 0, docs, 6, dummy, work, tables, dummy)
         assert (rc != 0) == want_err
-        rc = lib.tb_c4_pass_a_blk(None, dummy, dummy, dummy, dummy, 1, 1, dummy, dummy, dummy, 0, dummy, dummy,
-                                  dummy, dummy, dummy, dummy, dummy, lds, None, None, None, None, None, None)
+        rc = lib.tb_c4_pass_a_blk(None, dummy, docs, work, tables, dummy, None, None, None)
         assert (rc != 0) == want_err
 
 

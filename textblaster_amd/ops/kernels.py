@@ -4,6 +4,12 @@ helpers.
 Device memory comes from the native runtime layer (ops/hiprt.py: caching HBM allocator,
 ``DevArray`` views); kernels are launched on the calling thread's current hiprt stream. Every
 launch checks the returned hipError_t and raises — there is no silent fallback on a GPU box.
+
+The argument groups the document kernels share travel as structs (``LAUNCH_STRUCTS``: each the one
+mirror of its C struct at the head of kernels.hip's extern "C" block, sizes checked when
+``Kernels`` is created): ``Tables`` per batch, ``Docs`` and ``Work`` per launch, ``DictIn`` /
+``DictLines`` per content version / C4 step. ``_SIGS`` types them as ``POINTER(Struct)``, so a
+struct in the wrong place raises in Python.
 """
 from __future__ import annotations
 
@@ -20,43 +26,103 @@ _U32 = ctypes.c_uint32
 _I64 = ctypes.c_int64
 _SZ = ctypes.c_size_t
 
-# Bumped with every change of an entry point's signature in the table below: a stale
+# Bumped with every change of an entry point's signature or of a launch struct's layout: a stale
 # libtbhip.so with an older argument list would otherwise be called with the wrong arguments.
-ABI_VERSION = 24
+ABI_VERSION = 25
+
+
+def _ptr(t) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+class Tables(ctypes.Structure):
+    """TbTables: the Unicode property tables and the hash powers B^k / B^-k (``Kernels.tables``)."""
+    _fields_ = [("s1", _P), ("s2", _P), ("l1", _P), ("l2", _P), ("pw", _P), ("pw_n", _U32)]
+
+
+class Docs(ctypes.Structure):
+    """TbDocs: a content version (bytes, off), the launch positions perm[0 .. n_launch) and the
+    batch's dead marks; ``ndocs``: documents in the batch (the record stride)."""
+    _fields_ = [("bytes", _P), ("off", _P), ("perm", _P), ("dead", _P), ("n_launch", _I32), ("ndocs", _I32)]
+
+    @classmethod
+    def of(cls, bytes_, off, perm, n_launch, ndocs, dead=None):
+        if perm is not None and perm.numel() < n_launch:
+            raise DeviceError("launch: the permutation is shorter than the launch")
+        return cls(_ptr(bytes_), _ptr(off), _ptr(perm), _ptr(dead), int(n_launch), int(ndocs))
+
+
+class Work(ctypes.Structure):
+    """TbWork: what a document kernel writes (scratch slices by launch position, records, flags,
+    phase counters) and its dynamic LDS slice."""
+    _fields_ = [("scratch", _P), ("scratch_off", _P), ("rec", _P), ("flags", _P), ("prof", _P), ("lds_bytes", _U32)]
+
+    @classmethod
+    def of(cls, scratch, scratch_off, rec, flags, lds_bytes=0, prof=None):
+        return cls(_ptr(scratch), _ptr(scratch_off), _ptr(rec), _ptr(flags), _ptr(prof), int(lds_bytes))
+
+
+class DictIn(ctypes.Structure):
+    """devplan.h DictIn: the word sources of a content version's dictionary-script documents."""
+    _fields_ = [("moff", _P), ("bits", _P), ("words", _P)]
+
+
+class DictLines(ctypes.Structure):
+    """devplan.h DictLines (offsets int64, data uint32): host ICU line statistics of a C4 step's
+    dictionary-script documents."""
+    _fields_ = [("off", _P), ("data", _P)]
+
+
+class BadWords(ctypes.Structure):
+    """TbBadWords: the inputs of one C4BadWords step (``Kernels.badwords_match``)."""
+    _fields_ = [("root", _P), ("cjk", _P), ("table", _P), ("f1", _P), ("f2", _P), ("seg_doc", _P), ("seg_idx", _P),
+                ("root0", _I32), ("cjk0", _I32), ("dead_max", _U32), ("table_mask", _U32), ("seg_bytes", _U32)]
+
+
+class ResolveOut(ctypes.Structure):
+    """TbResolveOut: outputs and scratch of tb_resolve (``cap``: bytes of ``out``)."""
+    _fields_ = [("fail", _P), ("status", _P), ("fver", _P), ("lanes", _P), ("sc", _P), ("out", _P), ("cap", _I64),
+                ("out_off", _P), ("rows", _P), ("err", _P)]
+
+
+LAUNCH_STRUCTS = {Tables: "tb_sizeof_tables", Docs: "tb_sizeof_docs", Work: "tb_sizeof_work",
+                  DictIn: "tb_sizeof_dict_in", DictLines: "tb_sizeof_dict_lines", BadWords: "tb_sizeof_badwords",
+                  ResolveOut: "tb_sizeof_resolve_out"}
+
+_TAB, _DOCS, _WORK = ctypes.POINTER(Tables), ctypes.POINTER(Docs), ctypes.POINTER(Work)
 
 _SIGS = {
-    "tb_stage_analyze": [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _U32, _P, _I32, _I32, _P,
-                         _P, _P, _P, _P, _P],
-    "tb_gr_split_wave": [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _U32, _I32, _P,
-                         _I32],
-    "tb_c4_pass_a": [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _I32, _P, _P,
-                     _P, _P, _P],
-    "tb_stage_analyze_blk": [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P,
-                             _U32, _P, _P, _P, _I32, _U32, _I32, _P, _P, _I32, _P, _P, _P],
-    "tb_sizeof_pre_doc": [],
-    "tb_pre_decode": [_P, _P, _P, _P, _I32, _P, _P, _U32, _P, _P, _P, _P, _P],
-    "tb_gr_dup_split": [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _U32, _P],
-    "tb_sizeof_gr_export": [],
-    "tb_c4_pass_a_blk": [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _P,
-                         _P, _P, _P, _P],
-    "tb_gate": [_P, _P, _P, _I32, _I32, _P, _P, _I32],
-    "tb_sizeof_gate": [],
-    "tb_resolve": [_P, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P],
-    "tb_sizeof_resolve": [],
-    "tb_block_threads": [],
-    "tb_badwords_match": [_P, _P, _P, _I32, _P, _P, _I32, _I32, _P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                          _U32],
-    "tb_langid_mfma": [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, _P, _P, _I32, _P],
-    "tb_langid_prepare": [_P, _P, _P],
-    "tb_pre_wcanon": [_P, _P, _P, _P, _I32, _P, _P, _U32, _P, _U32, _P],
-    "tb_langid_aux_bytes": [],
+    # stream, plan, stage, docs, work, tables, line_stats, gr_export, dict_in
+    "tb_stage_analyze": [_P, _P, _P, _DOCS, _WORK, _TAB, _P, _P, ctypes.POINTER(DictIn)],
+    # stream, plan, stage, docs, work, tables, gr_export, n_split, split_bytes, line_stats, pre, dict_in
+    "tb_stage_analyze_blk": [_P, _P, _P, _DOCS, _WORK, _TAB, _P, _I32, _U32, _P, _P, ctypes.POINTER(DictIn)],
+    # stream, stage, gr_step, docs, n_tasks, gr_export, work, tables, (block, n_big | cursor)
+    "tb_gr_split_wave": [_P, _P, _I32, _DOCS, _I32, _P, _WORK, _TAB, _I32, _I32],
+    "tb_gr_dup_split": [_P, _P, _I32, _DOCS, _I32, _P, _WORK, _TAB, _P],
+    # stream, docs, pre, (tiles_max, cnt, tables | chunks_max, tables, flags)
+    "tb_pre_decode": [_P, _DOCS, _P, _U32, _P, _TAB],
+    "tb_pre_wcanon": [_P, _DOCS, _P, _U32, _TAB, _P],
+    # stream, c4, docs, work, tables, src, line_stats, c4_words, dict_lines
+    "tb_c4_pass_a": [_P, _P, _DOCS, _WORK, _TAB, _P, _P, _P, ctypes.POINTER(DictLines)],
+    "tb_c4_pass_a_blk": [_P, _P, _DOCS, _WORK, _TAB, _P, _P, _P, ctypes.POINTER(DictLines)],
     "tb_c4_pass_b": [_P, _P, _P, _I32, _P, _P, _P, _P, _P],
+    # stream, docs, tables, step inputs, matched
+    "tb_badwords_match": [_P, _DOCS, _TAB, ctypes.POINTER(BadWords), _P],
+    # stream, docs, tables, E, aux, WT, w_scale, bias, rec, width, prof
+    "tb_langid_mfma": [_P, _DOCS, _TAB, _P, _P, _P, ctypes.c_double, _P, _P, _I32, _P],
+    "tb_langid_prepare": [_P, _P, _P],
+    "tb_langid_aux_bytes": [],
+    "tb_gate": [_P, _P, _P, _I32, _I32, _P, _P, _I32],
+    # stream, rp, recs, nrecs, ndocs, flags, vb, vo, nver, outputs
+    "tb_resolve": [_P, _P, _P, _I32, _I32, _P, _P, _P, _I32, ctypes.POINTER(ResolveOut)],
     "tb_pow_table": [_P, _P, _U32],
     "tb_html_sizes": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P],
     "tb_html_scatter": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P, _P],
     "tb_bpe_count": [_P, _P, _P, _P, _P, _I32, _P],
-    "tb_sizeof_bpe": [],
-    "tb_abi_version": [],
+    "tb_abi_version": [], "tb_block_threads": [], "tb_phase_slots": [], "tb_stage_waves": [],
+    "tb_sizeof_pre_doc": [], "tb_sizeof_gr_export": [], "tb_sizeof_gate": [], "tb_sizeof_resolve": [],
+    "tb_sizeof_bpe": [], "tb_sizeof_plan": [], "tb_sizeof_stage": [], "tb_sizeof_c4": [],
+    **{name: [] for name in LAUNCH_STRUCTS.values()},
     # native runtime layer (csrc/hip/runtime.hip)
     "tbrt_device_count": [_P], "tbrt_set_device": [_I32], "tbrt_get_device": [_P], "tbrt_device_sync": [],
     "tbrt_mem_info": [_P, _P], "tbrt_malloc": [_P, _SZ], "tbrt_free": [_P], "tbrt_host_alloc": [_P, _SZ],
@@ -67,19 +133,7 @@ _SIGS = {
     "tbrt_stream_wait_event": [_P, _P], "tbrt_memcpy_h2d": [_P, _P, _SZ, _P], "tbrt_memcpy_d2h": [_P, _P, _SZ, _P],
     "tbrt_memcpy_d2d": [_P, _P, _SZ, _P], "tbrt_memset": [_P, _I32, _SZ, _P],
     "tb_scan_strided_i64": [_P, _P, _I64, _I64, _P],
-    "tb_phase_slots": [],
-    "tb_stage_waves": [],
-    "tb_sizeof_plan": [],
-    "tb_sizeof_stage": [],
-    "tb_sizeof_c4": [],
 }
-
-
-def _dict_ptrs(dict_in):
-    """(moff, bits, words) device arrays of docproc.h DictIn as three pointers (0 for None)."""
-    if dict_in is None:
-        return 0, 0, 0
-    return tuple(_ptr(a) for a in dict_in)
 
 
 # docproc.h PreDoc (checked against tb_sizeof_pre_doc)
@@ -127,13 +181,14 @@ def declare(lib: ctypes.CDLL) -> None:
         fn.restype = ctypes.c_size_t if name.startswith("tb_sizeof") else ctypes.c_int
 
 
-def _ptr(t) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 def _check(rc: int, what: str) -> None:
     if rc != 0:
         raise DeviceError(f"{what} failed with hipError_t {rc}")
+
+
+def _ptr_array8(arrays):
+    """Up to 8 device arrays as a void*[8] (null-padded)."""
+    return (ctypes.c_void_p * 8)(*([a.data_ptr() for a in arrays] + [None] * (8 - len(arrays))))
 
 
 class Kernels:
@@ -155,6 +210,9 @@ class Kernels:
         self.sizeof_gr_export = int(self.lib.tb_sizeof_gr_export())
         if int(self.lib.tb_sizeof_pre_doc()) != PRE_DOC.itemsize:
             raise DeviceError("libtbhip.so and ops/kernels.py disagree on PreDoc; rebuild")
+        for st, sizeof in LAUNCH_STRUCTS.items():
+            if int(getattr(self.lib, sizeof)()) != ctypes.sizeof(st):
+                raise DeviceError(f"libtbhip.so and ops/kernels.py disagree on {st.__name__}; rebuild")
         s1, s2, l1, l2 = h.ucd_tables()
         self.tabs = [hiprt.to_device(a) for a in (s1, s2, l1, l2)]
         self._pw = None
@@ -181,22 +239,21 @@ class Kernels:
             self._pw_n = cap
         return self._pw, self._pw_n
 
-    def stage_analyze(self, plan, stage, bytes_, off, perm, ndocs, scratch, scratch_off, pw, pw_n, rec, flags,
-                      lds_bytes=0, prof=None, waves=0, nblocks=0, dead=None, line_stats=None, gr_export=None,
-                      dict_in=None):
-        """k_stage_analyze_wave; ``dict_in`` = (moff, bits, words) device arrays or None each
-        (docproc.h DictIn: the word sources of dictionary-script documents); ``line_stats`` (uint32, >= 4 * (total bytes / 8 + 16 ndocs) + 16): the
-        C4 line export (docproc.h StageOut::line_stats), document d at 4 * (off[d] / 8 + 16 d).
-        ``gr_export`` (zeroed, >= nblocks descriptors): split mode, every launched document exports
-        its word arrays and gr_split_wave finishes its n-gram orders."""
-        t = self.tabs
-        if gr_export is not None and gr_export.nbytes < max(nblocks, 0) * self.sizeof_gr_export:
+    def tables(self, pw, pw_n) -> Tables:
+        """The tables struct of a batch: this device's Unicode tables + the batch's ``pow_table``."""
+        return Tables(*[t.data_ptr() for t in self.tabs], pw.data_ptr(), pw_n)
+
+    def stage_analyze(self, plan, stage, docs: Docs, work: Work, tables: Tables, line_stats=None, gr_export=None,
+                      dict_in: Optional[DictIn] = None):
+        """k_stage_analyze_wave over launch positions [0, docs.n_launch) (0: all); ``line_stats``
+        (uint32, >= 4 * (total bytes / 8 + 16 ndocs) + 16): the C4 line export (docproc.h
+        StageOut::line_stats), document d at 4 * (off[d] / 8 + 16 d). ``gr_export`` (zeroed, >=
+        n_launch descriptors): split mode, every launched document exports its word arrays and
+        gr_split_wave finishes its n-gram orders."""
+        if gr_export is not None and gr_export.nbytes < max(docs.n_launch, 0) * self.sizeof_gr_export:
             raise DeviceError("stage_analyze: export buffer too small")
-        rc = self.lib.tb_stage_analyze(
-            self.stream(), plan.data_ptr(), stage.data_ptr(), bytes_.data_ptr(), off.data_ptr(), _ptr(perm), ndocs,
-            scratch.data_ptr(), scratch_off.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(), t[1].data_ptr(),
-            t[2].data_ptr(), t[3].data_ptr(), rec.data_ptr(), flags.data_ptr(), lds_bytes, _ptr(prof), waves, nblocks,
-            _ptr(dead), _ptr(line_stats), _ptr(gr_export), *_dict_ptrs(dict_in))
+        rc = self.lib.tb_stage_analyze(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work, tables,
+                                       _ptr(line_stats), _ptr(gr_export), dict_in)
         _check(rc, "tb_stage_analyze")
 
     def gr_export_wave_bytes(self, n_docs: int) -> int:
@@ -204,99 +261,71 @@ class Kernels:
         documents its LDS arrays cannot hold (NgRest: 16-byte header + a u32 per document)."""
         return n_docs * self.sizeof_gr_export + 16 + 4 * n_docs
 
-    def gr_split_wave(self, stage, gr_step, perm, n_docs, n_tasks, ndocs, gr_export, pw, pw_n, rec, flags, lds_bytes,
-                      block=True, prof=None, n_big=0):
+    def gr_split_wave(self, stage, gr_step, docs: Docs, n_tasks, gr_export, work: Work, tables: Tables, block=True,
+                      n_big=0):
         """The n-gram orders of the wave documents stage_analyze exported (n_tasks = the
         GopherRepetition step's duplicated + top orders): launch positions [0, n_big) one wave per
         (document, order) (k_gr_split_wave), the rest with ``block`` one workgroup per document
         (k_gr_ngrams); without ``block`` k_gr_split_wave for all."""
-        if not 0 <= n_big <= n_docs:
+        if not 0 <= n_big <= docs.n_launch:
             raise DeviceError("gr_split_wave: n_big out of range")
-        if gr_export.nbytes < self.gr_export_wave_bytes(n_docs) or perm.numel() < n_docs:
+        if gr_export.nbytes < self.gr_export_wave_bytes(docs.n_launch):
             raise DeviceError("gr_split_wave: operand shapes")
-        t = self.tabs
-        rc = self.lib.tb_gr_split_wave(self.stream(), stage.data_ptr(), gr_step, perm.data_ptr(), n_docs, n_tasks,
-                                       ndocs, gr_export.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(),
-                                       t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), rec.data_ptr(),
-                                       flags.data_ptr(), lds_bytes, 1 if block else 0, _ptr(prof), int(n_big))
+        rc = self.lib.tb_gr_split_wave(self.stream(), stage.data_ptr(), gr_step, docs, n_tasks, gr_export.data_ptr(),
+                                       work, tables, 1 if block else 0, int(n_big))
         _check(rc, "tb_gr_split_wave")
 
-    def stage_analyze_blk(self, plan, stage, bytes_, off, perm_long, nlong, ndocs, scratch, scratch_off, pw, pw_n,
-                          rec, flags, lds_bytes=0, prof=None, dead=None, gr_export=None, n_split=0, split_bytes=0,
-                          threads=512, line_stats=None, pre=None, n_pre=0, dict_in=None):
+    def stage_analyze_blk(self, plan, stage, docs: Docs, work: Work, tables: Tables, gr_export=None, n_split=0,
+                          split_bytes=0, line_stats=None, pre=None, dict_in: Optional[DictIn] = None):
         """k_stage_analyze_blk; ``gr_export`` (zeroed, >= n_split descriptors): the first n_split
-        launch positions longer than ``split_bytes`` export their word arrays (split mode)."""
-        t = self.tabs
+        launch positions longer than ``split_bytes`` export their word arrays (split mode);
+        ``pre``: the pre-pass descriptors of every launched document."""
         if gr_export is not None and gr_export.nbytes < n_split * self.sizeof_gr_export:
             raise DeviceError("stage_analyze_blk: export buffer too small")
-        if not 0 <= n_split <= nlong:
+        if not 0 <= n_split <= docs.n_launch:
             raise DeviceError("stage_analyze_blk: n_split out of range")
-        rc = self.lib.tb_stage_analyze_blk(
-            self.stream(), plan.data_ptr(), stage.data_ptr(), bytes_.data_ptr(), off.data_ptr(), perm_long.data_ptr(),
-            nlong, ndocs, scratch.data_ptr(), scratch_off.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(),
-            t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), rec.data_ptr(), flags.data_ptr(), lds_bytes, _ptr(prof),
-            _ptr(dead), _ptr(gr_export), n_split if gr_export is not None else 0, split_bytes, int(threads),
-            _ptr(line_stats), _ptr(pre), int(n_pre) if pre is not None else 0, *_dict_ptrs(dict_in))
+        rc = self.lib.tb_stage_analyze_blk(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work, tables,
+                                           _ptr(gr_export), n_split if gr_export is not None else 0, split_bytes,
+                                           _ptr(line_stats), _ptr(pre), dict_in)
         _check(rc, "tb_stage_analyze_blk")
 
-    def pre_decode(self, bytes_, off, perm_pre, npre, dead, pre, tiles_max, cnt):
+    def pre_decode(self, docs: Docs, pre, tiles_max, cnt, tables: Tables):
         """k_pre_count / k_pre_decode / k_pre_wb: code points and word-break marks of
-        the first ``npre`` long documents over many workgroups; ``pre``: PRE_DOC descriptors
-        (device), ``cnt``: int64 [npre * tiles_max]."""
-        if perm_pre.numel() < npre or cnt.numel() < npre * tiles_max or pre.nbytes < npre * PRE_DOC.itemsize:
+        the first ``docs.n_launch`` long documents over many workgroups; ``pre``: PRE_DOC
+        descriptors (device), ``cnt``: int64 [n_launch * tiles_max]."""
+        npre = docs.n_launch
+        if cnt.numel() < npre * tiles_max or pre.nbytes < npre * PRE_DOC.itemsize:
             raise DeviceError("pre_decode: operand shapes")
-        t = self.tabs
-        rc = self.lib.tb_pre_decode(self.stream(), bytes_.data_ptr(), off.data_ptr(), perm_pre.data_ptr(), npre,
-                                    _ptr(dead), pre.data_ptr(), int(tiles_max), cnt.data_ptr(), t[0].data_ptr(),
-                                    t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr())
+        rc = self.lib.tb_pre_decode(self.stream(), docs, pre.data_ptr(), int(tiles_max), cnt.data_ptr(), tables)
         _check(rc, "tb_pre_decode")
 
-    def pre_wcanon(self, bytes_, off, perm_pre, npre, dead, pre, chunks_max, pw, pw_n, flags):
+    def pre_wcanon(self, docs: Docs, pre, chunks_max, tables: Tables, flags):
         """k_pre_wcanon / k_pre_wsum: GopherRepetition's word hashes, canonical word ids
-        and concatenation-hash arrays of the ``npre`` pre-pass documents over many workgroups (after
+        and concatenation-hash arrays of the pre-pass documents over many workgroups (after
         pre_decode; ``chunks_max`` >= ceil(max words / PRE_WCHUNK))."""
-        if perm_pre.numel() < npre or pre.nbytes < npre * PRE_DOC.itemsize or chunks_max <= 0:
+        if pre.nbytes < docs.n_launch * PRE_DOC.itemsize or chunks_max <= 0:
             raise DeviceError("pre_wcanon: operand shapes")
-        rc = self.lib.tb_pre_wcanon(self.stream(), bytes_.data_ptr(), off.data_ptr(), perm_pre.data_ptr(), npre,
-                                    _ptr(dead), pre.data_ptr(), int(chunks_max), pw.data_ptr(), pw_n,
-                                    flags.data_ptr())
+        rc = self.lib.tb_pre_wcanon(self.stream(), docs, pre.data_ptr(), int(chunks_max), tables, flags.data_ptr())
         _check(rc, "tb_pre_wcanon")
 
-    def gr_dup_split(self, stage, gr_step, perm, n_split, n_tasks, ndocs, gr_export, pw, pw_n, rec, flags, lds_bytes,
-                     cursor):
+    def gr_dup_split(self, stage, gr_step, docs: Docs, n_tasks, gr_export, work: Work, tables: Tables, cursor):
         """k_gr_dup_split: persistent workgroups take (split document, task) pairs from an atomic
         cursor (``cursor``: a uint32 device word of this launch, reset by the call; keep it alive
         until the kernel completes); n_tasks = the GopherRepetition step's duplicated + top n-gram
         orders + duplicated lines + paragraphs."""
-        if gr_export.nbytes < n_split * self.sizeof_gr_export or perm.numel() < n_split or cursor.nbytes < 4:
+        if gr_export.nbytes < docs.n_launch * self.sizeof_gr_export or cursor.nbytes < 4:
             raise DeviceError("gr_dup_split: operand shapes")
-        t = self.tabs
-        rc = self.lib.tb_gr_dup_split(self.stream(), stage.data_ptr(), gr_step, perm.data_ptr(), n_split, n_tasks, ndocs,
-                                      gr_export.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(), t[1].data_ptr(),
-                                      t[2].data_ptr(), t[3].data_ptr(), rec.data_ptr(), flags.data_ptr(), lds_bytes,
-                                      cursor.data_ptr())
+        rc = self.lib.tb_gr_dup_split(self.stream(), stage.data_ptr(), gr_step, docs, n_tasks, gr_export.data_ptr(),
+                                      work, tables, cursor.data_ptr())
         _check(rc, "tb_gr_dup_split")
 
-    def c4_pass_a_blk(self, c4, bytes_, off, perm_long, nlong, ndocs, scratch, scratch_off, pw, pw_n, rec, src, flags,
-                      lds_bytes=0, prof=None, dead=None, line_stats=None, c4_words=None, dict_lines=None):
-        t = self.tabs
-        dl = dict_lines or (None, None)
-        rc = self.lib.tb_c4_pass_a_blk(
-            self.stream(), c4.data_ptr(), bytes_.data_ptr(), off.data_ptr(), perm_long.data_ptr(), nlong, ndocs,
-            scratch.data_ptr(), scratch_off.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(), t[1].data_ptr(),
-            t[2].data_ptr(), t[3].data_ptr(), rec.data_ptr(), src.data_ptr(), flags.data_ptr(), lds_bytes, _ptr(prof),
-            _ptr(dead), _ptr(line_stats), _ptr(c4_words), _ptr(dl[0]), _ptr(dl[1]))
-        _check(rc, "tb_c4_pass_a_blk")
-
-    def badwords_match(self, bytes_, off, ndocs, table, fold, matched, root=None, cjk=None, root0=-1, cjk0=0,
-                       dead=None, dead_max=0, seg_bytes=2048, seg_doc=None, seg_idx=None):
+    def badwords_match(self, tables: Tables, bytes_, off, ndocs, table, fold, matched, root=None, cjk=None, root0=-1,
+                       cjk0=0, dead=None, dead_max=0, seg_bytes=2048, seg_doc=None, seg_idx=None):
         """k_badwords_match over documents [0, ndocs) of (bytes_, off): ``table`` is the hashed trie
         table (uint32 [4 * slots], csrc/common/badwords.h); per document root/cjk arrays, or one
         root0/cjk0 for all; documents with 0 < dead <= dead_max are skipped (matched -1). The first
         launch covers the first ``seg_bytes`` of every document; ``seg_doc`` / ``seg_idx`` (int32,
         the documents' further segments) add a second launch over those segments."""
-        t = self.tabs
-        f1, f2 = fold
         slots = table.numel() // 4
         if slots < 1 or slots & (slots - 1) or matched.numel() < ndocs or off.numel() < ndocs + 1:
             raise DeviceError("badwords_match: operand shapes")
@@ -309,11 +338,10 @@ class Kernels:
             nitems = ndocs if sd is None else sd.numel()
             if sd is not None and nitems == 0:
                 continue
-            rc = self.lib.tb_badwords_match(
-                self.stream(), bytes_.data_ptr(), off.data_ptr(), nitems, _ptr(root), _ptr(cjk), int(root0), int(cjk0),
-                _ptr(dead), int(dead_max), table.data_ptr(), slots - 1, t[0].data_ptr(), t[1].data_ptr(),
-                t[2].data_ptr(), t[3].data_ptr(), f1.data_ptr(), f2.data_ptr(), matched.data_ptr(), _ptr(sd), _ptr(si),
-                int(seg_bytes))
+            bw = BadWords(_ptr(root), _ptr(cjk), table.data_ptr(), fold[0].data_ptr(), fold[1].data_ptr(), _ptr(sd),
+                          _ptr(si), int(root0), int(cjk0), int(dead_max), slots - 1, int(seg_bytes))
+            rc = self.lib.tb_badwords_match(self.stream(), Docs.of(bytes_, off, None, nitems, ndocs, dead), tables,
+                                            bw, matched.data_ptr())
             _check(rc, "tb_badwords_match")
 
     def langid_prepare(self, E):
@@ -331,42 +359,34 @@ class Kernels:
         hiprt.current_stream().synchronize()
         return aux
 
-    def langid_mfma(self, bytes_, off, perm, ndocs, E, aux, WT, w_scale, bias, rec, width, prof=None):
+    def langid_mfma(self, docs: Docs, tables: Tables, E, aux, WT, w_scale, bias, rec, width, prof=None):
         """k_langid_mfma (v3 model): fastText int8 embedding bag + bf16 MFMA head, 16 documents per
-        tile; the language record of every document into ``rec`` (document d at rec[d * width]).
-        ``E``: the embedding table as E + 128, uint8 [buckets * 16], ``aux``: its pair table
-        (langid_prepare), ``WT``: bf16 bits [16 * 32] (head transposed), ``bias``: float32 [8]
-        (csrc/common/langid.h)."""
+        tile; the language record of every launched document into ``rec`` (document d at
+        rec[d * width]). ``E``: the embedding table as E + 128, uint8 [buckets * 16], ``aux``: its
+        pair table (langid_prepare), ``WT``: bf16 bits [16 * 32] (head transposed), ``bias``:
+        float32 [8] (csrc/common/langid.h)."""
         from .. import native
 
         h = native.host()
-        t = self.tabs
         if (E.numel() != h.LID_BUCKETS * h.LID_ROW_DIM or WT.numel() != 16 * h.LID_DIM or bias.numel() != h.LID_ROW
-                or width < 2 or rec.numel() < ndocs * width or not w_scale > 0
+                or width < 2 or rec.numel() < docs.n_launch * width or not w_scale > 0
                 or aux.numel() != int(self.lib.tb_langid_aux_bytes())):
             raise DeviceError("langid_mfma: operand shapes")
-        rc = self.lib.tb_langid_mfma(
-            self.stream(), bytes_.data_ptr(), off.data_ptr(), _ptr(perm), ndocs, t[0].data_ptr(), t[1].data_ptr(),
-            t[2].data_ptr(), t[3].data_ptr(), E.data_ptr(), aux.data_ptr(), WT.data_ptr(), float(w_scale),
-            bias.data_ptr(), rec.data_ptr(), width, _ptr(prof))
+        rc = self.lib.tb_langid_mfma(self.stream(), docs, tables, E.data_ptr(), aux.data_ptr(), WT.data_ptr(),
+                                     float(w_scale), bias.data_ptr(), rec.data_ptr(), width, _ptr(prof))
         _check(rc, "tb_langid_mfma")
 
-    def c4_pass_a(self, c4, bytes_, off, perm, ndocs, scratch, scratch_off, pw, pw_n, rec, src, flags, lds_bytes=0,
-                  prof=None, nblocks=0, dead=None, line_stats=None, c4_words=None, dict_lines=None):
-        """k_c4_pass_a; ``line_stats``: the line export of a stage over the same content version
-        (trimmed spans, word counts and longest words of the Rust lines: documents without a
-        citation skip decode, lines and words when split_paragraph is set). ``c4_words`` (uint32
-        per document, preset to 0xFFFFFFFF): the rewrite's word count on the export path.
-        ``dict_lines`` = (offsets int64, data uint32): host ICU line statistics of dictionary-script
-        documents (docproc.h DictLines)."""
-        t = self.tabs
-        dl = dict_lines or (None, None)
-        rc = self.lib.tb_c4_pass_a(
-            self.stream(), c4.data_ptr(), bytes_.data_ptr(), off.data_ptr(), _ptr(perm), ndocs, scratch.data_ptr(),
-            scratch_off.data_ptr(), pw.data_ptr(), pw_n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(),
-            t[3].data_ptr(), rec.data_ptr(), src.data_ptr(), flags.data_ptr(), lds_bytes, _ptr(prof), nblocks,
-            _ptr(dead), _ptr(line_stats), _ptr(c4_words), _ptr(dl[0]), _ptr(dl[1]))
-        _check(rc, "tb_c4_pass_a")
+    def c4_pass_a(self, c4, docs: Docs, work: Work, tables: Tables, src, line_stats=None, c4_words=None,
+                  dict_lines: Optional[DictLines] = None, blk=False):
+        """k_c4_pass_a (``blk``: k_c4_pass_a_blk, one workgroup per document); ``line_stats``: the
+        line export of a stage over the same content version (trimmed spans, word counts and
+        longest words of the Rust lines: documents without a citation skip decode, lines and words
+        when split_paragraph is set). ``c4_words`` (uint32 per document, preset to 0xFFFFFFFF):
+        the rewrite's word count on the export path."""
+        name = "tb_c4_pass_a_blk" if blk else "tb_c4_pass_a"
+        rc = getattr(self.lib, name)(self.stream(), c4.data_ptr(), docs, work, tables, src.data_ptr(),
+                                     _ptr(line_stats), _ptr(c4_words), dict_lines)
+        _check(rc, name)
 
     def c4_pass_b(self, bytes_, off, ndocs, scratch, scratch_off, src, new_off, out):
         rc = self.lib.tb_c4_pass_b(self.stream(), bytes_.data_ptr(), off.data_ptr(), ndocs, scratch.data_ptr(),
@@ -383,9 +403,8 @@ class Kernels:
             raise DeviceError("gate: operand shapes")
         if any(r.numel() < need * ndocs for r in recs):
             raise DeviceError("gate: a record buffer is smaller than the gate's steps read")
-        arr = (ctypes.c_void_p * 8)(*([r.data_ptr() for r in recs] + [None] * (8 - len(recs))))
-        rc = self.lib.tb_gate(self.stream(), gate.data_ptr(), ctypes.cast(arr, ctypes.c_void_p), len(recs), ndocs,
-                              flags.data_ptr(), dead.data_ptr(), code)
+        rc = self.lib.tb_gate(self.stream(), gate.data_ptr(), ctypes.cast(_ptr_array8(recs), ctypes.c_void_p),
+                              len(recs), ndocs, flags.data_ptr(), dead.data_ptr(), code)
         _check(rc, "tb_gate")
 
     def bpe_tables(self, spec) -> BpeTables:
@@ -413,12 +432,10 @@ class Kernels:
                 or lanes.numel() < 4 * ndocs or sc.numel() < 4 * ndocs or out_off.numel() < ndocs + 1
                 or rows.numel() < ndocs or err.numel() < 1 or any(vo.numel() != ndocs + 1 for _, vo in versions)):
             raise DeviceError("resolve: operand shapes")
-        ra = (ctypes.c_void_p * 8)(*([r.data_ptr() for r in recs] + [None] * (8 - len(recs))))
-        vb = (ctypes.c_void_p * 8)(*([b.data_ptr() for b, _ in versions] + [None] * (8 - len(versions))))
-        vo = (ctypes.c_void_p * 8)(*([o.data_ptr() for _, o in versions] + [None] * (8 - len(versions))))
-        rc = self.lib.tb_resolve(self.stream(), rp.data_ptr(), ctypes.cast(ra, ctypes.c_void_p), len(recs), ndocs,
-                                 flags.data_ptr(), ctypes.cast(vb, ctypes.c_void_p), ctypes.cast(vo, ctypes.c_void_p),
-                                 len(versions), fail.data_ptr(), status.data_ptr(), fver.data_ptr(), lanes.data_ptr(),
-                                 sc.data_ptr(), out.data_ptr(), out.numel(), out_off.data_ptr(), rows.data_ptr(),
-                                 err.data_ptr())
+        ra, vb, vo = (ctypes.cast(_ptr_array8(x), ctypes.c_void_p)
+                      for x in (recs, [b for b, _ in versions], [o for _, o in versions]))
+        bufs = ResolveOut(fail.data_ptr(), status.data_ptr(), fver.data_ptr(), lanes.data_ptr(), sc.data_ptr(),
+                          out.data_ptr(), out.numel(), out_off.data_ptr(), rows.data_ptr(), err.data_ptr())
+        rc = self.lib.tb_resolve(self.stream(), rp.data_ptr(), ra, len(recs), ndocs, flags.data_ptr(), vb, vo,
+                                 len(versions), bufs)
         _check(rc, "tb_resolve")

@@ -15,7 +15,7 @@ import numpy as np
 
 from .. import native
 from ..errors import DeviceError
-from ..ops.kernels import PRE_DOC, PRE_TILE, PRE_WCHUNK
+from ..ops.kernels import PRE_DOC, PRE_TILE, PRE_WCHUNK, DictIn, DictLines, Docs, Work
 from ..utils import metrics, tracing
 from .plan import ExecPlan
 from . import tuning
@@ -248,6 +248,34 @@ class _Slot:
         self.s_h2d = self.s_d2h = None
 
 
+class _Batch:
+    """What DeviceRunner's per-pass methods share while they queue one batch."""
+
+    def __init__(self, slot: _Slot, data: np.ndarray, off: np.ndarray, bw, n_stages: int):
+        self.slot, self.data, self.off, self.bw = slot, data, off, bw
+        self.ndocs = len(off) - 1
+        self.lens = np.diff(off)
+        # _scratch_layout: launch order (longest first; [0, n_long) run one workgroup each), the
+        # lengths in that order, scratch slice offsets by launch position
+        self.perm = self.lens_perm = self.scratch_off = None
+        self.n_long = 0
+        # _upload: staged inputs, bad-words arrays by (step | version, name), DictIn by content
+        # version, DictLines by C4 step, the arena, the tables struct, flags, dead marks
+        self.d_bytes = self.d_off = self.d_perm = self.d_soff = None
+        self.bw_dev, self.dict_in, self.dict_lines = {}, {}, {}
+        self.scratch = self.tables = self.flags = self.dead = None
+        self.versions = {}  # content version -> (bytes, offsets, byte bound)
+        self.keep: List = []  # what must outlive the batch's kernels
+        # the passes: compute stream, per version the event its content is ready after and its C4
+        # line export, the events the compute stream joins at the end
+        self.main = self.lstats = None
+        self.ready, self.tails = {}, []
+        self.pass_idx = 0
+        self.pre_v0 = None  # (descriptors, n_pre) of the version-0 pre-pass
+        self.stage_recs: List = [None] * n_stages
+        self.c4_recs, self.bw_matched = {}, {}
+
+
 class PendingBatch:
     """A submitted batch: kernels and D2H copies are queued on the stream; ``wait()`` blocks on
     the completion event and returns host views of the results."""
@@ -424,7 +452,15 @@ class DeviceRunner:
             hiprt.set_device(self.device)
         self.plan = plan
         self.steps = steps_native
-        h = native.host()
+        self._init_streams(max_batch_bytes)
+        self._init_device_state(langid, token_counters)
+        self._init_operating_points()
+        self._next_slot = 0
+        self._bw_table = None  # (gen, device copy) of the hashed bad-words trie table
+        self._bw_fold = None
+
+    def _init_streams(self, max_batch_bytes: int) -> None:
+        hiprt, tu = self.rt, self.tune
         # Streams. The box exposes GPU_MAX_HW_QUEUES=4 hardware queues per process. The default
         # layout ("6") has exactly four streams that carry kernels — per slot one compute stream
         # (wave kernels, C4, language-id head, gates) and one side stream (long-document
@@ -462,6 +498,12 @@ class DeviceRunner:
                 sl.main = sl.s_c4 = hiprt.Stream()
                 sl.s_blk = sl.s_lid = sl.s_c4blk = hiprt.Stream(priority=blk_prio)
                 sl.s_h2d, sl.s_d2h = h2d, d2h
+
+    def _init_device_state(self, langid, token_counters) -> None:
+        """The kernels and the device copies of everything the plan compiles to (plan, stage, C4,
+        gate and resolve blobs, the language-id model, tokenizer tables, the power table), uploaded
+        on the first slot's compute stream."""
+        hiprt, tu, plan, steps_native, h = self.rt, self.tune, self.plan, self.steps, native.host()
         init = self.slots[0].main
         with hiprt.stream(init):
             from ..ops.kernels import Kernels
@@ -513,6 +555,10 @@ class DeviceRunner:
             with tracing.trace_range("tb.init.pow_table"):
                 self.k.pow_table(1 << 22)
             init.synchronize()  # uploads and the table are complete before any slot stream reads them
+
+    def _init_operating_points(self) -> None:
+        """LDS slices, length thresholds and split settings of the launches (pipeline/tuning.py)."""
+        tu, plan, steps_native, h = self.tune, self.plan, self.steps, native.host()
         # LDS arena per document (one wave per workgroup): the stage kernel is built for W
         # waves/SIMD (tb_stage_waves) = 4 W waves/CU, so 160 KB / 4 W each costs no occupancy
         self.stage_waves = int(self.k.lib.tb_stage_waves())
@@ -570,9 +616,6 @@ class DeviceRunner:
         self.phase_totals: Dict[str, np.ndarray] = {}
         self.phase_docs: Dict[str, int] = {}
         self.copy_threads = tu.copy_threads
-        self._next_slot = 0
-        self._bw_table = None  # (gen, device copy) of the hashed bad-words trie table
-        self._bw_fold = None
 
     def bind_thread(self) -> None:
         """Make this runner's GPU the current device of the calling thread (HIP's current device
@@ -649,10 +692,11 @@ class DeviceRunner:
             out.append(dev[o:o + a.nbytes].view(a.dtype) if a.nbytes else dev[o:o].view(a.dtype))
         return out, dev
 
-    def _pre_decode(self, vb, vo, d_perm, long_lens: np.ndarray, dead, keep, flags=None, with_words=False):
+    def _pre_decode(self, b: "_Batch", vb, vo, dead):
         """SURVEY 5.7 pre-pass for the longest documents (launch positions [0, n_pre), sorted by
         length): device arrays for their code points and word-break marks, filled by k_pre_* on
         the current stream. Returns (PreDoc descriptors as a uint8 device array, n_pre)."""
+        long_lens = b.lens_perm[:b.n_long]
         if self.pre_doc_bytes <= 0 or not len(long_lens):
             return None, 0
         big = np.nonzero(long_lens >= self.pre_doc_bytes)[0]
@@ -672,7 +716,7 @@ class DeviceRunner:
         per = sz_off + sz_prop + sz_wbm + 2 * sz_nl + sz_wt + 4 * sz_w + sz_wa
         # GopherRepetition's word arrays (k_pre_wcanon): wh / wk / wpb (8 B), wslot / wid / wl (4 B)
         # per word, the 1.5 W + 2-slot table, 4 sums per 2048-word chunk
-        wcanon = bool(self.gr_split) and with_words
+        wcanon = bool(self.gr_split) and self.pre_wcanon
         if wcanon:
             sz_w8 = al(8 * (lens + 2))
             sz_tab = al(8 * (lens + lens // 2 + 3))
@@ -714,19 +758,22 @@ class DeviceRunner:
         d_pre.copy_from_host(hp, rt.current_stream())
         tiles_max = int((int(lens.max()) + PRE_TILE - 1) // PRE_TILE)
         cnt = rt.empty(n_pre * tiles_max, np.int64)
-        self.k.pre_decode(vb, vo, d_perm[:n_pre], n_pre, dead, d_pre, tiles_max, cnt)
+        docs = Docs.of(vb, vo, b.d_perm[:n_pre], n_pre, b.ndocs, dead)
+        self.k.pre_decode(docs, d_pre, tiles_max, cnt, b.tables)
         if wcanon:
-            pw, pw_n = self.k.pow_table(int(lens.max()) + 16)
+            # (the batch's power table covers 2 * the longest document)
             chunks_max = int((int(lens.max()) + 1 + PRE_WCHUNK - 1) // PRE_WCHUNK)
-            self.k.pre_wcanon(vb, vo, d_perm[:n_pre], n_pre, dead, d_pre, chunks_max, pw, pw_n, flags)
-        keep += [buf, d_pre, cnt, hp]
+            self.k.pre_wcanon(docs, d_pre, chunks_max, b.tables, b.flags)
+        b.keep += [buf, d_pre, cnt, hp]
         return d_pre, n_pre
 
-    def _langid(self, vb, vo, d_perm, ndocs, scratch, d_soff, rec, width, flags, prof):
-        """Language-id records of a content version: k_langid_mfma (embedding bag + bf16 MFMA
-        head, one 16-document tile per workgroup; no scratch)."""
-        self.k.langid_mfma(vb, vo, d_perm, ndocs, self.lid_E, self.lid_aux, self.lid_WT, self.lid_w_scale,
-                           self.lid_b, rec, width, prof)
+    def _langid(self, b: "_Batch", vb, vo, s: int, rec, lid_at):
+        """Language-id records of stage ``s`` on the current stream: k_langid_mfma (embedding bag +
+        bf16 MFMA head, one 16-document tile per workgroup; no scratch) per language-id step."""
+        docs = Docs.of(vb, vo, b.d_perm, b.ndocs, b.ndocs)
+        for width, prefix in lid_at:
+            self.k.langid_mfma(docs, b.tables, self.lid_E, self.lid_aux, self.lid_WT, self.lid_w_scale, self.lid_b,
+                               rec[prefix * b.ndocs:], width, self._prof_buf(b.ndocs, b.keep, f"langid{s}"))
 
     def _scratch_for(self, slot: _Slot, nbytes: int, which: str = "stage"):
         attr = "scratch" if which == "stage" else "scratch_c4"
@@ -737,9 +784,6 @@ class DeviceRunner:
             cur = self.rt.empty(int(nbytes * 1.25) + (1 << 20), np.uint8)
             setattr(slot, attr, cur)
         return cur
-
-    def _record(self, stream):
-        return stream.record()
 
     def _ktimed(self, keep, name: str):
         """Context manager: HIP events around the launches inside it on the current stream; the
@@ -805,11 +849,41 @@ class DeviceRunner:
         import time
 
         rt = self.rt
-        h = native.host()
-        ndocs = len(off) - 1
-        lens = np.diff(off)
-        perm = launch_order(lens)
-        lens_perm = lens[perm]
+        b = _Batch(slot, data, off, bw, len(self.plan.stages))
+        self._scratch_layout(b)
+        self._upload(b)
+        t1 = time.perf_counter()
+        # Independent work runs concurrently on side streams (events order the dependencies):
+        #   language-id bag (s_lid) | long-doc workgroup kernels (s_blk) | wave kernels (main)
+        #   | C4 pass A/B of the same content version (s_c4, own scratch arena)
+        # Block and wave kernels touch disjoint documents, so they share the stage arena.
+        main = b.main = rt.current_stream()
+        b.ready = {0: main.record()}
+        for ver in range(self.plan.n_versions):
+            main.wait_event(b.ready[ver])
+            # uint32 [4 * (bytes / 8 + 16 * documents) + 16]: document d's region at
+            # 4 * (off[d] / 8 + 16 d) (docproc.h line_stats_base)
+            b.lstats = None
+            if ver in self.line_stats_stage:
+                b.lstats = rt.empty(4 * (b.versions[ver][2] // 8 + 16 * b.ndocs) + 16, np.uint32)
+                b.keep.append(b.lstats)
+            for s, sv in enumerate(self.plan.stage_version):
+                if sv == ver:
+                    self._stage(b, ver, s)
+            for i in self.plan.c4_steps:
+                if self.plan.steps[i].version_in == ver:
+                    self._c4_step(b, ver, i)
+        for ev in b.tails:
+            main.wait_event(ev)
+        self._badwords(b)
+        res_d = self._resolve(b)
+        return self._download(b, res_d, t0, t1)
+
+    def _scratch_layout(self, b: "_Batch") -> None:
+        """The launch order and the scratch slice of every document."""
+        lens, ndocs = b.lens, b.ndocs
+        b.perm = perm = launch_order(lens)
+        b.lens_perm = lens[perm]
         # scratch slice per document (devplan.h scratch_bytes_for_dev): the split rate for the
         # documents whose n-gram orders run in split tasks (k_gr_dup_split over the workgroup
         # documents past split_doc_bytes, k_gr_split_wave over wave documents past ngram_big_bytes)
@@ -827,11 +901,16 @@ class DeviceRunner:
         # slices in dispatch (perm) order: scratch_off[k] is the slice of the k-th launched
         # document, so the waves resident at one time share one contiguous window of the arena
         # (TLB and cache locality) instead of slices scattered over ~50 GB
-        scratch_off = np.zeros(ndocs + 1, dtype=np.int64)
-        np.cumsum(per_doc[perm], out=scratch_off[1:])
-        maxlen = int(lens.max()) if ndocs else 0
-        n_long = int(np.count_nonzero(lens > self.long_doc_bytes)) if self.long_doc_bytes > 0 else 0
+        b.scratch_off = np.zeros(ndocs + 1, dtype=np.int64)
+        np.cumsum(per_doc[perm], out=b.scratch_off[1:])
         # perm is longest first: [0, n_long) workgroup docs, then the wave docs
+        b.n_long = int(np.count_nonzero(lens > self.long_doc_bytes)) if self.long_doc_bytes > 0 else 0
+
+    def _upload(self, b: "_Batch") -> None:
+        """One upload of the batch's inputs (text, offsets, launch order, scratch layout, bad-words
+        and dictionary arrays), then the buffers every pass shares: arena, tables, flags, dead."""
+        rt, h = self.rt, native.host()
+        data, off, lens, ndocs, bw = b.data, b.off, b.lens, b.ndocs, b.bw
         direct_keep: List = []
         # per-document bad-words roots / CJK flags and the long documents' segment lists travel in
         # the same upload
@@ -862,267 +941,260 @@ class DeviceRunner:
                             dict_c4_keys.append(i)
                             dict_arrays += [lo, ld]
         with tracing.trace_range("tb.stage_h2d"):
-            staged_views, staged = self._stage_inputs(
-                slot, [data if len(data) else np.zeros(1, np.uint8), off, perm, scratch_off]
+            views, staged = self._stage_inputs(
+                b.slot, [data if len(data) else np.zeros(1, np.uint8), off, b.perm, b.scratch_off]
                 + [np.ascontiguousarray(a) for _, a in bw_arrays] + dict_arrays, direct_keep)
-        d_bytes, d_off, d_perm, d_soff = staged_views[:4]
-        bw_dev = {key: d for (key, _), d in zip(bw_arrays, staged_views[4:4 + len(bw_arrays)])}
+        b.d_bytes, b.d_off, b.d_perm, b.d_soff = views[:4]
+        b.bw_dev = {key: d for (key, _), d in zip(bw_arrays, views[4:4 + len(bw_arrays)])}
         # per content version: the word sources of its dictionary-script documents (DictIn)
-        nd_arr = len(dict_arrays)
-        dv = staged_views[len(staged_views) - nd_arr:] if nd_arr else []
-        dict_in = {0: (dv[0], dv[1], None)} if nd_arr else {}
-        dict_lines = {i: (dv[2 + 2 * k], dv[3 + 2 * k]) for k, i in enumerate(dict_c4_keys)}
-        scratch = self._scratch_for(slot, int(scratch_off[-1]))
+        dv = views[len(views) - len(dict_arrays):] if dict_arrays else []
+        b.dict_in = {0: DictIn(dv[0].data_ptr(), dv[1].data_ptr(), None)} if dict_arrays else {}
+        b.dict_lines = {i: DictLines(dv[2 + 2 * k].data_ptr(), dv[3 + 2 * k].data_ptr())
+                        for k, i in enumerate(dict_c4_keys)}
+        b.scratch = self._scratch_for(b.slot, int(b.scratch_off[-1]))
         # grows (new tensor, on this slot's stream) only for documents over 2 MB; the batch keeps a
         # reference to the table it used, so the other slot's kernels never see it freed
-        pw, pw_n = self.k.pow_table(2 * maxlen + 64)
-        flags = rt.zeros(ndocs, np.int32)
-        dead = rt.zeros(ndocs, np.uint8) if self.gate_ts else None
-        pass_idx = 0
-        t1 = time.perf_counter()
-        versions = {0: (d_bytes, d_off, len(data))}
-        stage_recs_d: List = [None] * len(self.plan.stages)
-        c4_recs_d = {}
-        keep = [staged, scratch, pw] + direct_keep
-        # Independent work runs concurrently on side streams (events order the dependencies):
-        #   language-id bag (s_lid) | long-doc workgroup kernels (s_blk) | wave kernels (main)
-        #   | C4 pass A/B of the same content version (s_c4, own scratch arena)
-        # Block and wave kernels touch disjoint documents, so they share the stage arena.
-        main = rt.current_stream()
-        ready = {0: self._record(main)}
-        tails = []
-        c4_scratch = None
-        pre_v0 = None  # (descriptors, n_pre) of the version-0 pre-pass
-        for ver in range(self.plan.n_versions):
-            vb, vo, vlen = versions[ver]
-            main.wait_event(ready[ver])
-            # uint32 [4 * (bytes / 8 + 16 * documents) + 16]: document d's region at
-            # 4 * (off[d] / 8 + 16 d) (docproc.h line_stats_base)
-            lstats = None
-            if ver in self.line_stats_stage:
-                lstats = rt.empty(4 * (vlen // 8 + 16 * ndocs) + 16, np.uint32)
-                keep.append(lstats)
-            for s, sv in enumerate(self.plan.stage_version):
-                if sv != ver:
+        pw, pw_n = self.k.pow_table(2 * (int(lens.max()) if ndocs else 0) + 64)
+        b.tables = self.k.tables(pw, pw_n)
+        b.flags = rt.zeros(ndocs, np.int32)
+        b.dead = rt.zeros(ndocs, np.uint8) if self.gate_ts else None
+        b.versions = {0: (b.d_bytes, b.d_off, len(data))}
+        b.keep = [staged, b.scratch, pw] + direct_keep
+
+    def _gate(self, b: "_Batch", rec) -> None:
+        """End of pass ``b.pass_idx``: on the current stream its gate (if it has one) marks the
+        documents a step of the pass filtered, so the later passes skip them."""
+        p = b.pass_idx
+        if p in self.gate_ts:
+            self.k.gate(self.gate_ts[p], [rec], b.ndocs, b.flags, b.dead, p + 1, 0, self.gate_need[p])
+        b.pass_idx += 1
+
+    def _stage(self, b: "_Batch", ver: int, s: int) -> None:
+        """Stage ``s`` over content version ``ver``: language ID (as a gated pass of its own first,
+        or next to the stage kernels), the long documents' workgroups, the wave kernels, the gate."""
+        rt, slot, main, ndocs = self.rt, b.slot, b.main, b.ndocs
+        vb, vo, _ = b.versions[ver]
+        width_total, layout = self.stage_layout[s]
+        rec = rt.zeros(width_total * ndocs, np.int64)
+        lid_at = [(width, prefix) for kind, width, prefix in layout if kind == KIND_LANGID]
+        ev_pre = main.record()  # rec zeroed
+        b.keep.append(ev_pre)
+        ev_lid = ev_blk = None
+        prof = self._prof_buf(ndocs, b.keep, f"stage{s}")
+        lid_pass = ("lid", s) in self.passes
+        if lid_pass:
+            # language-id pass first (records + gate on the side stream); the stage kernels
+            # below skip the documents it filters
+            slot.s_lid.wait_event(ev_pre)
+            with rt.stream(slot.s_lid):
+                with self._ktimed(b.keep, "langid"):
+                    self._langid(b, vb, vo, s, rec, lid_at)
+                self._gate(b, rec)
+                ev_pre = slot.s_lid.record()
+                b.keep.append(ev_pre)
+            main.wait_event(ev_pre)
+        skip = b.dead if b.pass_idx > 0 else None
+        ls_out = b.lstats if self.line_stats_stage.get(ver) == s else None
+        # long documents first: with the 4-stream layout the workgroup kernels and the
+        # language-id bag share the side stream, and the long-document tail must start early
+        if b.n_long:
+            slot.s_blk.wait_event(ev_pre)
+            ev_blk = self._stage_blk(b, ver, s, rec, prof, skip, ls_out)
+        if lid_at and not lid_pass:
+            # language ID next to the stage kernels: it writes only its own record columns
+            slot.s_lid.wait_event(ev_pre)
+            with rt.stream(slot.s_lid), self._ktimed(b.keep, "langid"):
+                self._langid(b, vb, vo, s, rec, lid_at)
+                ev_lid = slot.s_lid.record()
+                b.keep.append(ev_lid)
+        if b.n_long < ndocs:
+            self._stage_wave(b, ver, s, rec, prof, skip, ls_out)
+        if ev_lid is not None:
+            main.wait_event(ev_lid)
+        if ev_blk is not None:
+            main.wait_event(ev_blk)
+        self._gate(b, rec)
+        b.stage_recs[s] = rec
+
+    def _stage_blk(self, b: "_Batch", ver: int, s: int, rec, prof, skip, ls_out):
+        """The long documents of a stage, one workgroup each on the side stream (launch positions
+        [0, n_long)); returns the event after them."""
+        rt, slot, ndocs, n_long = self.rt, b.slot, b.ndocs, b.n_long
+        vb, vo, _ = b.versions[ver]
+        n_split, gx = 0, None
+        if s in self.gr_split and self.split_doc_bytes > 0:
+            # launch positions [0, n_split) hold every document over the split size
+            huge = np.nonzero(b.lens_perm[:n_long] > self.split_doc_bytes)[0]
+            if len(huge):
+                n_split = int(huge[-1]) + 1
+                # zeroed on the stream of the kernels that write and read it
+                gx = rt.zeros(n_split * self.k.sizeof_gr_export, np.uint8, slot.s_blk)
+                b.keep.append(gx)
+        # the split export slots are indexed by launch position
+        esz = self.k.sizeof_gr_export
+        with rt.stream(slot.s_blk), self._ktimed(b.keep, f"stage{s}_blk"):
+            # (the original text only: the host knows no lengths of rewritten versions); once
+            # per batch: every stage reading version 0 reuses it (read-only, same stream)
+            if ver == 0 and b.pre_v0 is None:
+                b.pre_v0 = self._pre_decode(b, vb, vo, skip)
+            pre, n_pre = b.pre_v0 if ver == 0 else (None, 0)
+            # launch positions [0, n_pre): the pre-pass kernel instantiation, the rest the common one
+            for a0, a1, with_pre in ((0, n_pre, True), (n_pre, n_long, False)):
+                if a1 <= a0:
                     continue
-                width_total, layout = self.stage_layout[s]
-                rec = rt.zeros(width_total * ndocs, np.int64)
-                lid_at = [(width, prefix) for kind, width, prefix in layout if kind == KIND_LANGID]
-                ev_pre = self._record(main)  # rec zeroed
-                keep.append(ev_pre)
-                ev_lid = ev_blk = None
-                prof = self._prof_buf(ndocs, keep, f"stage{s}")
-                lid_pass = ("lid", s) in self.passes
-                if lid_pass:
-                    # language-id pass first (records + gate on the side stream); the stage kernels
-                    # below skip the documents it filters
-                    slot.s_lid.wait_event(ev_pre)
-                    with rt.stream(slot.s_lid):
-                        with self._ktimed(keep, "langid"):
-                            for width, prefix in lid_at:
-                                self._langid(vb, vo, d_perm, ndocs, scratch, d_soff, rec[prefix * ndocs:], width,
-                                             flags, self._prof_buf(ndocs, keep, f"langid{s}"))
-                        if pass_idx in self.gate_ts:
-                            self.k.gate(self.gate_ts[pass_idx], [rec], ndocs, flags, dead, pass_idx + 1, 0,
-                                        self.gate_need[pass_idx])
-                        ev_pre = self._record(slot.s_lid)
-                        keep.append(ev_pre)
-                    main.wait_event(ev_pre)
-                    pass_idx += 1
-                skip = dead if pass_idx > 0 else None
-                ls_out = lstats if self.line_stats_stage.get(ver) == s else None
-                # long documents first: with the 4-stream layout the workgroup kernels and the
-                # language-id bag share the side stream, and the long-document tail must start early
-                if n_long:
-                    slot.s_blk.wait_event(ev_pre)
-                    n_split, gx = 0, None
-                    if s in self.gr_split and self.split_doc_bytes > 0:
-                        # launch positions [0, n_split) hold every document over the split size
-                        huge = np.nonzero(lens[perm[:n_long]] > self.split_doc_bytes)[0]
-                        if len(huge):
-                            n_split = int(huge[-1]) + 1
-                            # zeroed on the stream of the kernels that write and read it
-                            gx = rt.zeros(n_split * self.k.sizeof_gr_export, np.uint8, slot.s_blk)
-                            keep.append(gx)
-                    # the split export slots are indexed by launch position
-                    esz = self.k.sizeof_gr_export
-                    with rt.stream(slot.s_blk), self._ktimed(keep, f"stage{s}_blk"):
-                        # (the original text only: the host knows no lengths of rewritten versions); once
-                        # per batch: every stage reading version 0 reuses it (read-only, same stream)
-                        if ver == 0 and pre_v0 is None:
-                            pre_v0 = self._pre_decode(vb, vo, d_perm, lens[perm[:n_long]], skip, keep, flags,
-                                                      self.pre_wcanon)
-                        pre, n_pre = pre_v0 if ver == 0 else (None, 0)
-                        # launch positions [0, n_pre): the pre-pass kernel instantiation, the rest the common one
-                        bt = self.block_threads
-                        segs = ((0, n_pre, bt, True), (n_pre, n_long, bt, False))
-                        for a0, a1, thr, with_pre in segs:
-                            if a1 <= a0:
-                                continue
-                            ns = max(0, min(n_split, a1) - a0)
-                            self.k.stage_analyze_blk(self.plan_t, self.stage_ts[s], vb, vo, d_perm[a0:a1], a1 - a0,
-                                                     ndocs, scratch, d_soff[a0:], pw, pw_n, rec, flags,
-                                                     self.lds_bytes_blk, prof, skip,
-                                                     gx[a0 * esz:] if (gx is not None and ns) else None, ns,
-                                                     self.split_doc_bytes, thr, ls_out,
-                                                     pre if with_pre else None, a1 - a0 if with_pre else 0,
-                                                     dict_in.get(ver))
-                        if n_split:
-                            gr_pos, n_tasks = self.gr_split[s]
-                            cur = rt.empty(1, np.uint32)
-                            keep.append(cur)
-                            self.k.gr_dup_split(self.stage_ts[s], gr_pos, d_perm[:n_split], n_split, n_tasks, ndocs,
-                                                gx, pw, pw_n, rec, flags, self.lds_bytes_dup, cur)
-                        ev_blk = self._record(slot.s_blk)
-                        keep.append(ev_blk)
-                if lid_at and not lid_pass:
-                    # language ID next to the stage kernels: it writes only its own record columns
-                    slot.s_lid.wait_event(ev_pre)
-                    with rt.stream(slot.s_lid), self._ktimed(keep, "langid"):
-                        for width, prefix in lid_at:
-                            self._langid(vb, vo, d_perm, ndocs, scratch, d_soff, rec[prefix * ndocs:], width,
-                                         flags, self._prof_buf(ndocs, keep, f"langid{s}"))
-                        ev_lid = self._record(slot.s_lid)
-                        keep.append(ev_lid)
-                if n_long < ndocs:
-                    nw = ndocs - n_long
-                    gxw = None
-                    if s in self.gr_split:
-                        # split mode: the wave documents' n-gram orders run one wave per (document,
-                        # order) after the stage kernel (k_gr_split_wave)
-                        gxw = rt.zeros(self.k.gr_export_wave_bytes(nw), np.uint8)
-                        keep.append(gxw)
-                    with self._ktimed(keep, f"stage{s}"):
-                        self.k.stage_analyze(self.plan_t, self.stage_ts[s], vb, vo, d_perm[n_long:], ndocs,
-                                             scratch, d_soff[n_long:], pw, pw_n, rec, flags,
-                                             self.lds_bytes, prof, self.stage_waves, nw, skip, ls_out, gxw,
-                                             dict_in.get(ver))
-                        if gxw is not None:
-                            gr_pos, n_tasks = self.gr_split[s]
-                            # wave documents longer than ngram_big_bytes (a prefix: perm is longest
-                            # first) take one wave per order, the rest one workgroup each
-                            n_big = int(np.count_nonzero(lens_perm[n_long:] > self.ngram_big_bytes))
-                            self.k.gr_split_wave(self.stage_ts[s], gr_pos, d_perm[n_long:], nw, n_tasks - 2, ndocs,
-                                                 gxw, pw, pw_n, rec, flags, self.lds_bytes_split, self.ngram_block,
-                                                 self._prof_buf(ndocs, keep, f"ngram{s}"), n_big)
-                if ev_lid is not None:
-                    main.wait_event(ev_lid)
-                if ev_blk is not None:
-                    main.wait_event(ev_blk)
-                if pass_idx in self.gate_ts:
-                    self.k.gate(self.gate_ts[pass_idx], [rec], ndocs, flags, dead, pass_idx + 1, 0,
-                                        self.gate_need[pass_idx])
-                pass_idx += 1
-                stage_recs_d[s] = rec
-            c4_here = [i for i in self.plan.c4_steps if self.plan.steps[i].version_in == ver]
-            for i in c4_here:
-                # The C4 pass reuses the stage arena: it starts after every stage kernel of its
-                # content version (it waits for the gate on the compute stream), and the stages of
-                # the next version start after its pass B (ready event).
-                c4_scratch = scratch
-                rec = rt.zeros(7 * ndocs, np.int64)
-                src = rt.zeros(2 * ndocs, np.int64)
-                new_off = rt.zeros(ndocs + 1, np.int64)
-                # the rewrite's word count per document (kNoWords unless C4 pass A's export path
-                # set it): the word source of the next version's dictionary-script documents
-                c4w = None
-                if self.dict_marks and ver in dict_in:
-                    c4w = rt.empty(ndocs, np.uint32).fill_(0xFF)
-                    keep.append(c4w)
-                    dict_in[ver + 1] = (None, None, c4w)
-                cap = vlen + self.c4_growth * ndocs + 16  # device rewrites never grow more (kC4MaxGrowth)
-                out = rt.empty(cap, np.uint8)
-                ev_main = self._record(main)
-                slot.s_c4.wait_event(ev_main)
-                slot.s_c4.wait_event(ready[ver])
-                keep.append(ev_main)
-                skip = dead if pass_idx > 0 else None
-                prof = self._prof_buf(ndocs, keep, f"c4_step{i}")
-                ev_c4blk = None
-                if n_long:
-                    # long documents (workgroup kernel) next to the wave kernel: disjoint docs
-                    ev_c4 = self._record(slot.s_c4)
-                    slot.s_c4blk.wait_event(ev_c4)
-                    keep.append(ev_c4)
-                    with rt.stream(slot.s_c4blk):
-                        self.k.c4_pass_a_blk(self.c4_ts[i], vb, vo, d_perm[:n_long], n_long, ndocs, c4_scratch,
-                                             d_soff, pw, pw_n, rec, src, flags, self.lds_bytes_blk, prof, skip,
-                                             lstats, c4w, dict_lines.get(i))
-                        ev_c4blk = self._record(slot.s_c4blk)
-                        keep.append(ev_c4blk)
-                with rt.stream(slot.s_c4), self._ktimed(keep, f"c4_step{i}"):
-                    if n_long < ndocs:
-                        self.k.c4_pass_a(self.c4_ts[i], vb, vo, d_perm[n_long:], ndocs, c4_scratch, d_soff[n_long:], pw,
-                                         pw_n, rec, src, flags, self.lds_bytes_c4, prof, ndocs - n_long, skip,
-                                         lstats, c4w, dict_lines.get(i))
-                    if ev_c4blk is not None:
-                        slot.s_c4.wait_event(ev_c4blk)
-                    rt.scan_strided_i64(src[1:], 2, ndocs, new_off[1:])
-                    self.k.c4_pass_b(vb, vo, ndocs, c4_scratch, d_soff, src, new_off, out)
-                    if pass_idx in self.gate_ts:
-                        self.k.gate(self.gate_ts[pass_idx], [rec], ndocs, flags, dead, pass_idx + 1, 0,
-                                        self.gate_need[pass_idx])
-                    ev = self._record(slot.s_c4)
-                pass_idx += 1
-                versions[ver + 1] = (out, new_off, cap)
-                ready[ver + 1] = ev
-                tails.append(ev)
-                c4_recs_d[i] = rec
-                keep.append(src)
-        for ev in tails:
-            main.wait_event(ev)
-        bw_d = {}
-        for i in sorted(bw):
-            # C4BadWords: match every document that reached the step on the content version it
-            # reads; the keep-fraction draws and the decision stay on the host (document order)
-            x = bw[i]
-            sp = self.plan.steps[i]
-            vb, vo, _ = versions[sp.version_in]
+                ns = max(0, min(n_split, a1) - a0)
+                self.k.stage_analyze_blk(
+                    self.plan_t, self.stage_ts[s], Docs.of(vb, vo, b.d_perm[a0:a1], a1 - a0, ndocs, skip),
+                    Work.of(b.scratch, b.d_soff[a0:], rec, b.flags, self.lds_bytes_blk, prof), b.tables,
+                    gx[a0 * esz:] if (gx is not None and ns) else None, ns, self.split_doc_bytes, ls_out,
+                    pre if with_pre else None, b.dict_in.get(ver))
+            if n_split:
+                gr_pos, n_tasks = self.gr_split[s]
+                cur = rt.empty(1, np.uint32)
+                b.keep.append(cur)
+                self.k.gr_dup_split(self.stage_ts[s], gr_pos, Docs.of(None, None, b.d_perm[:n_split], n_split, ndocs),
+                                    n_tasks, gx, Work.of(None, None, rec, b.flags, self.lds_bytes_dup), b.tables, cur)
+            ev_blk = slot.s_blk.record()
+            b.keep.append(ev_blk)
+        return ev_blk
+
+    def _stage_wave(self, b: "_Batch", ver: int, s: int, rec, prof, skip, ls_out) -> None:
+        """The wave documents of a stage on the compute stream (launch positions [n_long, ndocs))."""
+        ndocs, n_long = b.ndocs, b.n_long
+        vb, vo, _ = b.versions[ver]
+        nw = ndocs - n_long
+        gxw = None
+        if s in self.gr_split:
+            # split mode: the wave documents' n-gram orders run one wave per (document,
+            # order) after the stage kernel (k_gr_split_wave)
+            gxw = self.rt.zeros(self.k.gr_export_wave_bytes(nw), np.uint8)
+            b.keep.append(gxw)
+        with self._ktimed(b.keep, f"stage{s}"):
+            self.k.stage_analyze(self.plan_t, self.stage_ts[s], Docs.of(vb, vo, b.d_perm[n_long:], nw, ndocs, skip),
+                                 Work.of(b.scratch, b.d_soff[n_long:], rec, b.flags, self.lds_bytes, prof), b.tables,
+                                 ls_out, gxw, b.dict_in.get(ver))
+            if gxw is not None:
+                gr_pos, n_tasks = self.gr_split[s]
+                # wave documents longer than ngram_big_bytes (a prefix: perm is longest
+                # first) take one wave per order, the rest one workgroup each
+                n_big = int(np.count_nonzero(b.lens_perm[n_long:] > self.ngram_big_bytes))
+                work = Work.of(None, None, rec, b.flags, self.lds_bytes_split,
+                               self._prof_buf(ndocs, b.keep, f"ngram{s}"))
+                self.k.gr_split_wave(self.stage_ts[s], gr_pos, Docs.of(None, None, b.d_perm[n_long:], nw, ndocs),
+                                     n_tasks - 2, gxw, work, b.tables, self.ngram_block, n_big)
+
+    def _c4_step(self, b: "_Batch", ver: int, i: int) -> None:
+        """C4 step ``i`` over content version ``ver``: pass A (workgroup and wave kernels side by
+        side), the scan of the new lengths, pass B into version ``ver + 1``, the gate."""
+        rt, slot, ndocs, n_long = self.rt, b.slot, b.ndocs, b.n_long
+        vb, vo, vlen = b.versions[ver]
+        # The C4 pass reuses the stage arena: it starts after every stage kernel of its
+        # content version (it waits for the gate on the compute stream), and the stages of
+        # the next version start after its pass B (ready event).
+        rec = rt.zeros(7 * ndocs, np.int64)
+        src = rt.zeros(2 * ndocs, np.int64)
+        new_off = rt.zeros(ndocs + 1, np.int64)
+        # the rewrite's word count per document (kNoWords unless C4 pass A's export path
+        # set it): the word source of the next version's dictionary-script documents
+        c4w = None
+        if self.dict_marks and ver in b.dict_in:
+            c4w = rt.empty(ndocs, np.uint32).fill_(0xFF)
+            b.keep.append(c4w)
+            b.dict_in[ver + 1] = DictIn(None, None, c4w.data_ptr())
+        cap = vlen + self.c4_growth * ndocs + 16  # device rewrites never grow more (kC4MaxGrowth)
+        out = rt.empty(cap, np.uint8)
+        ev_main = b.main.record()
+        slot.s_c4.wait_event(ev_main)
+        slot.s_c4.wait_event(b.ready[ver])
+        b.keep.append(ev_main)
+        skip = b.dead if b.pass_idx > 0 else None
+        prof = self._prof_buf(ndocs, b.keep, f"c4_step{i}")
+        ev_c4blk = None
+        if n_long:
+            # long documents (workgroup kernel) next to the wave kernel: disjoint docs
+            ev_c4 = slot.s_c4.record()
+            slot.s_c4blk.wait_event(ev_c4)
+            b.keep.append(ev_c4)
+            with rt.stream(slot.s_c4blk):
+                self.k.c4_pass_a(self.c4_ts[i], Docs.of(vb, vo, b.d_perm[:n_long], n_long, ndocs, skip),
+                                 Work.of(b.scratch, b.d_soff, rec, b.flags, self.lds_bytes_blk, prof), b.tables, src,
+                                 b.lstats, c4w, b.dict_lines.get(i), blk=True)
+                ev_c4blk = slot.s_c4blk.record()
+                b.keep.append(ev_c4blk)
+        with rt.stream(slot.s_c4), self._ktimed(b.keep, f"c4_step{i}"):
+            if n_long < ndocs:
+                self.k.c4_pass_a(self.c4_ts[i], Docs.of(vb, vo, b.d_perm[n_long:], ndocs - n_long, ndocs, skip),
+                                 Work.of(b.scratch, b.d_soff[n_long:], rec, b.flags, self.lds_bytes_c4, prof),
+                                 b.tables, src, b.lstats, c4w, b.dict_lines.get(i))
+            if ev_c4blk is not None:
+                slot.s_c4.wait_event(ev_c4blk)
+            rt.scan_strided_i64(src[1:], 2, ndocs, new_off[1:])
+            self.k.c4_pass_b(vb, vo, ndocs, b.scratch, b.d_soff, src, new_off, out)
+            self._gate(b, rec)
+            ev = slot.s_c4.record()
+        b.versions[ver + 1] = (out, new_off, cap)
+        b.ready[ver + 1] = ev
+        b.tails.append(ev)
+        b.c4_recs[i] = rec
+        b.keep.append(src)
+
+    def _badwords(self, b: "_Batch") -> None:
+        """C4BadWords: match every document that reached the step on the content version it
+        reads; the keep-fraction draws and the decision stay on the host (document order)."""
+        for i in sorted(b.bw):
+            x = b.bw[i]
+            v = self.plan.steps[i].version_in
+            vb, vo, _ = b.versions[v]
             table, fold = self._bw_tables(x)
-            m = rt.empty(max(ndocs, 1), np.int8)
-            v = sp.version_in
-            with self._ktimed(keep, "badwords"):
-                self.k.badwords_match(vb, vo, ndocs, table, fold, m, bw_dev.get((i, "root")), bw_dev.get((i, "cjk")),
-                                      x.root0, x.cjk0, dead, self.bw_dead_max[i], BW_SEG_BYTES,
-                                      bw_dev.get((v, "seg_doc")), bw_dev.get((v, "seg_idx")))
-            keep += [table, m]
-            bw_d[i] = m
-        res_d = None
-        if self.resolve_t is not None:
-            # K16 on the compute stream after every pass: first failure, status, and the final
-            # contents of kept / excluded documents compacted into one buffer (the host then only
-            # formats metadata). Output bound: a C4 rewrite grows a document by <= C4_MAX_GROWTH.
-            recs = [r for r in stage_recs_d] + [c4_recs_d[i] for i in self.plan.c4_steps]
-            vlist = [(versions[v][0], versions[v][1]) for v in range(self.plan.n_versions)]
-            cap = len(data) + self.c4_growth * (self.plan.n_versions - 1) * ndocs + 16
-            r_fail = rt.empty(ndocs, np.int32)
-            r_status = rt.empty(ndocs, np.uint8)
-            r_ver = rt.empty(ndocs, np.uint8)
-            r_lanes = rt.empty(4 * ndocs, np.int64)
-            r_sc = rt.empty(4 * ndocs, np.int64)
-            r_out = rt.empty(max(cap, 1), np.uint8)
-            r_off = rt.zeros(ndocs + 1, np.int64)
-            r_rows = rt.empty(ndocs, np.int32)
-            r_err = rt.zeros(1, np.int32)
-            if any(r.numel() < need * ndocs for r, need in zip(recs, self.resolve_need)):
-                raise DeviceError("resolve: a record buffer is smaller than the resolve plan reads")
-            with self._ktimed(keep, "resolve"):
-                self.k.resolve(self.resolve_t, recs, ndocs, flags.view(np.uint32), vlist, r_fail, r_status, r_ver,
-                               r_lanes, r_sc, r_out, r_off, r_rows, r_err)
-            keep += [r_fail, r_status, r_ver, r_lanes, r_sc, r_out, r_off, r_rows, r_err]
-            res_d = (r_fail, r_status, r_out, r_off, r_rows, r_err, r_ver)
-            for si, tabs in self.bpe:
-                # the kept outputs are r_out[r_off[k]:r_off[k + 1]], k < the kept count (the last
-                # entry of the kept-count scan, read by the kernel)
-                r_tok = rt.empty(ndocs, np.int32)
-                with self._ktimed(keep, "bpe_count"):
-                    self.k.bpe_count(tabs, r_out, r_off, r_sc[3 * ndocs - 1:3 * ndocs], ndocs, r_tok)
-                keep.append(r_tok)
-                res_d = res_d + ((si, r_tok),)
-        # D2H into pinned host buffers on the download stream (the slot's compute stream in the
-        # 4-stream layout: it is last in line there anyway), then one completion event
-        done = self._record(main)
-        d2h_s = slot.s_d2h
+            m = self.rt.empty(max(b.ndocs, 1), np.int8)
+            with self._ktimed(b.keep, "badwords"):
+                self.k.badwords_match(b.tables, vb, vo, b.ndocs, table, fold, m, b.bw_dev.get((i, "root")),
+                                      b.bw_dev.get((i, "cjk")), x.root0, x.cjk0, b.dead, self.bw_dead_max[i],
+                                      BW_SEG_BYTES, b.bw_dev.get((v, "seg_doc")), b.bw_dev.get((v, "seg_idx")))
+            b.keep += [table, m]
+            b.bw_matched[i] = m
+
+    def _resolve(self, b: "_Batch"):
+        """K16 on the compute stream after every pass: first failure, status, and the final
+        contents of kept / excluded documents compacted into one buffer (the host then only
+        formats metadata), then the token counts of the kept outputs. Returns the device results
+        to download, or None without a resolve plan."""
+        if self.resolve_t is None:
+            return None
+        rt, ndocs = self.rt, b.ndocs
+        # Output bound: a C4 rewrite grows a document by <= C4_MAX_GROWTH.
+        recs = [r for r in b.stage_recs] + [b.c4_recs[i] for i in self.plan.c4_steps]
+        vlist = [(b.versions[v][0], b.versions[v][1]) for v in range(self.plan.n_versions)]
+        cap = len(b.data) + self.c4_growth * (self.plan.n_versions - 1) * ndocs + 16
+        r_fail, r_status, r_ver = rt.empty(ndocs, np.int32), rt.empty(ndocs, np.uint8), rt.empty(ndocs, np.uint8)
+        r_lanes, r_sc = rt.empty(4 * ndocs, np.int64), rt.empty(4 * ndocs, np.int64)
+        r_out, r_off = rt.empty(max(cap, 1), np.uint8), rt.zeros(ndocs + 1, np.int64)
+        r_rows, r_err = rt.empty(ndocs, np.int32), rt.zeros(1, np.int32)
+        if any(r.numel() < need * ndocs for r, need in zip(recs, self.resolve_need)):
+            raise DeviceError("resolve: a record buffer is smaller than the resolve plan reads")
+        with self._ktimed(b.keep, "resolve"):
+            self.k.resolve(self.resolve_t, recs, ndocs, b.flags.view(np.uint32), vlist, r_fail, r_status, r_ver,
+                           r_lanes, r_sc, r_out, r_off, r_rows, r_err)
+        b.keep += [r_fail, r_status, r_ver, r_lanes, r_sc, r_out, r_off, r_rows, r_err]
+        res_d = (r_fail, r_status, r_out, r_off, r_rows, r_err, r_ver)
+        for si, tabs in self.bpe:
+            # the kept outputs are r_out[r_off[k]:r_off[k + 1]], k < the kept count (the last
+            # entry of the kept-count scan, read by the kernel)
+            r_tok = rt.empty(ndocs, np.int32)
+            with self._ktimed(b.keep, "bpe_count"):
+                self.k.bpe_count(tabs, r_out, r_off, r_sc[3 * ndocs - 1:3 * ndocs], ndocs, r_tok)
+            b.keep.append(r_tok)
+            res_d = res_d + ((si, r_tok),)
+        return res_d
+
+    def _download(self, b: "_Batch", res_d, t0: float, t1: float) -> PendingBatch:
+        """D2H into pinned host buffers on the download stream (the slot's compute stream in the
+        4-stream layout: it is last in line there anyway), then one completion event."""
+        import time
+
+        rt, main, versions = self.rt, b.main, b.versions
+        done = main.record()
+        d2h_s = b.slot.s_d2h
         if d2h_s is not main:
             d2h_s.wait_event(done)
 
@@ -1131,13 +1203,12 @@ class DeviceRunner:
             t.copy_to_host(ht, d2h_s)
             return ht
 
-        h_stage = [d2h(r) if r is not None else None for r in stage_recs_d]
-        h_c4 = {i: d2h(r) for i, r in c4_recs_d.items()}
+        h_stage = [d2h(r) if r is not None else None for r in b.stage_recs]
+        h_c4 = {i: d2h(r) for i, r in b.c4_recs.items()}
         h_versions = {}
         h_res = None
         if res_d is not None:
             h_res = tuple(d2h(t) for t in res_d[:7]) + tuple((si, d2h(t)) for si, t in res_d[7:])
-        if h_res is not None:
             # K16: the compacted outputs replace the versions on the host path; they stay in HBM
             # (downloaded only if the host has to assemble this batch itself)
             h_versions = LazyVersions({v: versions[v][:2] for v in range(1, self.plan.n_versions)})
@@ -1145,14 +1216,14 @@ class DeviceRunner:
             for ver in range(1, self.plan.n_versions):
                 vb, vo, _ = versions[ver]
                 h_versions[ver] = (d2h(vb), d2h(vo))
-        h_flags = d2h(flags)
-        h_dead = d2h(dead) if dead is not None else None
-        h_bw = {i: d2h(m) for i, m in bw_d.items()}
-        ev = self._record(d2h_s)
-        keep += [stage_recs_d, c4_recs_d, versions, flags, dead, ready, tails, done]
+        h_flags = d2h(b.flags)
+        h_dead = d2h(b.dead) if b.dead is not None else None
+        h_bw = {i: d2h(m) for i, m in b.bw_matched.items()}
+        ev = d2h_s.record()
+        b.keep += [b.stage_recs, b.c4_recs, versions, b.flags, b.dead, b.ready, b.tails, done]
         t2 = time.perf_counter()
-        return PendingBatch(self, ndocs, ev, h_stage, h_c4, h_versions, h_flags,
-                            {"stage_h2d": t1 - t0, "launch": t2 - t1}, keep, h_dead, h_res, h_bw)
+        return PendingBatch(self, b.ndocs, ev, h_stage, h_c4, h_versions, h_flags,
+                            {"stage_h2d": t1 - t0, "launch": t2 - t1}, b.keep, h_dead, h_res, h_bw)
 
     def run(self, data: np.ndarray, off: np.ndarray, bw: Optional[Dict[int, BwInput]] = None) -> DeviceResult:
         return self.submit(data, off, bw).wait()
