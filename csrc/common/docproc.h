@@ -1067,6 +1067,9 @@ TB_HD bool ci_contains(const uint8_t* b, uint32_t n, const char* pat, int plen) 
 // computes everything except the duplicated n-gram orders and exports the per-word arrays those
 // need (all in the document's HBM scratch slice); then one workgroup per (document, order) —
 // k_gr_dup_split — canonicalises its order, marks repeats and runs its greedy walk, in parallel.
+// One-wave documents export W, bs, be, b, free_base / free_cap and valid only (wid, WL, K, PB stay
+// null): the n-gram kernels build their own word arrays on chip, and k_gr_words fills the four
+// in for the documents that take the generic per-order code.
 struct GrExport {
   const uint32_t* wid;   // canonical word ids
   const uint32_t* WL;    // byte prefix of word lengths
@@ -1508,6 +1511,26 @@ TB_HD void gopher_rep_record(DocCtx<P>& x, const DevStep& ds, const uint8_t* b, 
       x.set_flag(DOC_NEEDS_CPU);
       return;
     }
+    if (ngrams && ex) {
+      // One-wave documents in split mode: the n-gram kernels rebuild everything word-level (ids,
+      // byte prefix, concatenation hashes) from the word spans and the text, so nothing is hashed
+      // or canonicalised here and only the spans are exported. (Nothing is allocated after this
+      // point, so the top of the LDS slice needs no release.)
+      const uint64_t base = (x.used + 255) & ~255ull;
+      x.par.single([&]() {
+        for (int t = 0; t < ds.n_top + ds.n_dup; ++t) r[rec_gr_fixed() + t] = 0;
+        ex->bs = w.bs; ex->be = w.be;
+        ex->b = b_export ? b_export : b;
+        ex->free_base = x.scr + base;
+        ex->free_cap = x.cap > base ? x.cap - base : 0;
+        ex->W = W;
+        ex->valid = x.overflow ? 0u : 1u;
+      });
+      x.par.sync();
+      x.stamp(PH_GR_WORDS);
+      x.reset(mark);
+      return;
+    }
   }
   uint32_t* wid = nullptr;
   uint32_t* WL = nullptr;
@@ -1528,17 +1551,11 @@ TB_HD void gopher_rep_record(DocCtx<P>& x, const DevStep& ds, const uint8_t* b, 
     WL = ex ? x.template alloc<uint32_t>(W + 1) : x.template alloc_hot_keep<uint32_t>(W + 1, tab_bytes);
     K = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
     PB = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
-    // One-wave documents export these arrays and read neither the code point arrays nor the prefix
-    // hashes (the top of the LDS slice) after the word hashes: the slice's top is released right
-    // there, so the word canonicalisation table lands in the LDS (it was in HBM for most ~1 KB
-    // documents) and the hashes go to the bottom.
-    const bool early = P::kWaves == 1 && release_props && ex != nullptr;
     const auto mw = x.mark();
-    uint64_t* wh = early ? x.template alloc_hot<uint64_t>(W + 1) : x.template alloc_hot_hi<uint64_t>(W + 1);
+    uint64_t* wh = x.template alloc_hot_hi<uint64_t>(W + 1);
     if (x.overflow) return;
     x.par.for_n(W, [&](uint32_t k) { wh[k] = span_hash8(x, ph, w.bs[k], w.be[k]); });
     x.par.sync();
-    if (early) x.release_hi();
     x.stamp(PH_GR_WH);
     canonicalize(
         x, W, [&](uint32_t k) { return dev_key(wh[k], w.be[k] - w.bs[k]); },

@@ -28,7 +28,7 @@ _SZ = ctypes.c_size_t
 
 # Bumped with every change of an entry point's signature or of a launch struct's layout: a stale
 # libtbhip.so with an older argument list would otherwise be called with the wrong arguments.
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 def _ptr(t) -> Optional[int]:
@@ -257,16 +257,18 @@ class Kernels:
         _check(rc, "tb_stage_analyze")
 
     def gr_export_wave_bytes(self, n_docs: int) -> int:
-        """Bytes of a zeroed wave export buffer: n_docs descriptors, then k_gr_ngrams' list of the
-        documents its LDS arrays cannot hold (NgRest: 16-byte header + a u32 per document)."""
-        return n_docs * self.sizeof_gr_export + 16 + 4 * n_docs
+        """Bytes of a zeroed wave export buffer: n_docs descriptors, then the k_gr_ngrams kernels'
+        two lists of the documents their LDS arrays cannot hold (NgRest: 32-byte header + two u32
+        per document)."""
+        return n_docs * self.sizeof_gr_export + 32 + 8 * n_docs
 
     def gr_split_wave(self, stage, gr_step, docs: Docs, n_tasks, gr_export, work: Work, tables: Tables, block=True,
                       n_big=0):
         """The n-gram orders of the wave documents stage_analyze exported (n_tasks = the
-        GopherRepetition step's duplicated + top orders): launch positions [0, n_big) one wave per
-        (document, order) (k_gr_split_wave), the rest with ``block`` one workgroup per document
-        (k_gr_ngrams); without ``block`` k_gr_split_wave for all."""
+        GopherRepetition step's duplicated + top orders). With ``block`` one workgroup per
+        document builds the word arrays on chip (k_gr_ngrams: launch positions [0, n_big) with
+        512-word arrays, the rest with 256-word ones, what they leave with 1024-word ones);
+        without it the generic code, one wave per (document, order) (k_gr_words, k_gr_split_wave)."""
         if not 0 <= n_big <= docs.n_launch:
             raise DeviceError("gr_split_wave: n_big out of range")
         if gr_export.nbytes < self.gr_export_wave_bytes(docs.n_launch):

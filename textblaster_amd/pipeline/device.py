@@ -602,10 +602,10 @@ class DeviceRunner:
         # overrides for A/B runs (larger only: smaller slices send documents to the CPU path)
         self.scratch_rates = (max(int(h.SCRATCH_PER_BYTE), tu.scratch_rate[0]),
                               max(int(h.SCRATCH_PER_BYTE_SPLIT), tu.scratch_rate[1]))
-        # wave documents finish their n-gram orders in one wave per (document, order)
-        # (k_gr_split_wave) or, below ngram_big_bytes, one workgroup per document (k_gr_ngrams:
-        # 256 words, ~5.5 bytes per word on natural text; a document with more words runs the
-        # generic code in that workgroup)
+        # wave documents finish their n-gram orders one workgroup per document, which builds the
+        # word arrays on chip (k_gr_ngrams: 256 words up to ngram_big_bytes, ~5.5 bytes per word
+        # on natural text, 512 words above; documents with more words go to a 1024-word kernel,
+        # then to the generic code); ngram_block=0: the generic code, one wave per (document, order)
         self.lds_bytes_split = tu.lds_bytes_split
         self.ngram_block = tu.ngram_block
         self.ngram_big_bytes = tu.ngram_big_bytes
@@ -1065,8 +1065,8 @@ class DeviceRunner:
         nw = ndocs - n_long
         gxw = None
         if s in self.gr_split:
-            # split mode: the wave documents' n-gram orders run one wave per (document,
-            # order) after the stage kernel (k_gr_split_wave)
+            # split mode: the wave documents' n-gram orders run after the stage kernel
+            # (k_gr_ngrams), from the word spans it exports
             gxw = self.rt.zeros(self.k.gr_export_wave_bytes(nw), np.uint8)
             b.keep.append(gxw)
         with self._ktimed(b.keep, f"stage{s}"):
@@ -1076,7 +1076,7 @@ class DeviceRunner:
             if gxw is not None:
                 gr_pos, n_tasks = self.gr_split[s]
                 # wave documents longer than ngram_big_bytes (a prefix: perm is longest
-                # first) take one wave per order, the rest one workgroup each
+                # first) take the 512-word workgroups, the rest the 256-word ones
                 n_big = int(np.count_nonzero(b.lens_perm[n_long:] > self.ngram_big_bytes))
                 work = Work.of(None, None, rec, b.flags, self.lds_bytes_split,
                                self._prof_buf(ndocs, b.keep, f"ngram{s}"))

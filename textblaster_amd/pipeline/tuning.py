@@ -35,13 +35,13 @@ class DeviceTuning:
     lds_bytes_c4: int = 2560       # C4 pass A wave slice (per-line arrays only)
     lds_bytes_blk: int = 49152     # long-document workgroups: three per CU
     lds_bytes_dup: int = 0         # k_gr_dup_split slice; 0: = lds_bytes_blk
-    lds_bytes_split: int = 5120    # k_gr_split_wave: 8 waves/SIMD (2.68 vs 2.80 ms at 6 KB, profiles/r8_wpe/)
+    lds_bytes_split: int = 5120    # k_gr_split_wave (ngram_block=0): 8 waves/SIMD (2.68 vs 2.80 ms at 6 KB, profiles/r8_wpe/)
     # -- document routing thresholds (bytes) --
     long_doc_bytes: int = 4096     # one workgroup instead of one wave (profiles/r2_c5/long_doc_threshold.txt)
     split_doc_bytes: int = 32768   # n-gram orders in k_gr_dup_split (config 5: 147.6 -> 152 K docs/s, profiles/r8_c5/)
     pre_doc_bytes: int = 262144    # multi-workgroup pre-pass (k_pre_*): ~1 MB docs 1,001 -> 1,136 docs/s (profiles/r5_pre/)
-    ngram_big_bytes: int = 1200    # wave documents above: one wave per n-gram order (k_gr_split_wave)
-    ngram_block: bool = True       # wave documents below: one workgroup per document (k_gr_ngrams)
+    ngram_big_bytes: int = 1200    # wave documents above: 512-word n-gram workgroups (k_gr_ngrams_big)
+    ngram_block: bool = True       # wave documents: one workgroup per document (k_gr_ngrams); 0: generic code
     pre_wcanon: bool = True        # pre-pass documents hash/canonicalise words in k_pre_wcanon
     scratch_rate: Tuple[int, int] = (0, 0)  # scratch bytes per text byte (one pass, split); 0: devplan.h
     # -- device work placement (off = the host does it; A/B and debugging) --
