@@ -27,6 +27,7 @@
 
 #include "../common/docproc.h"
 #include "../common/gate.h"
+#include "../common/metafmt.h"
 #include "../common/badwords.h"
 
 using namespace tb;
@@ -2046,6 +2047,128 @@ __global__ __launch_bounds__(64) void k_pre_wsum(const int32_t* __restrict__ per
   if (MODE == 1 && lane == 0) pre[s].wready = 1;
 }
 
+// K18: the metadata column of the compacted outputs (csrc/common/metafmt.h). Output row pos
+// (kept rows first, then excluded, the order of k_compact's `rows`) is formatted from the records
+// of document rows[pos]; nk / nx are the last entries of the kept / excluded count scans.
+struct MetaTokens {
+  const int32_t* p[kMaxMetaTokens];  // k_bpe_count results by kept output
+};
+
+// One lane per output row: byte length (0 past the last row) and validity. An unformattable row
+// sets its bit of the error word (the host then assembles the batch itself).
+__global__ __launch_bounds__(256) void k_meta_size(const DevResolve* __restrict__ rp, const DevMetaPlan* __restrict__ mp,
+                                                   GateRecs recs, int32_t ndocs, const int32_t* __restrict__ fail,
+                                                   const int32_t* __restrict__ rows, const int64_t* __restrict__ sc,
+                                                   MetaTokens tk, int64_t* __restrict__ lens,
+                                                   uint8_t* __restrict__ valid, int32_t* __restrict__ err) {
+  const int pos = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pos >= ndocs) return;
+  const int64_t n = ndocs;
+  const int64_t nk = sc[3 * n - 1], n_rows = nk + sc[4 * n - 1];
+  uint32_t len = 0;
+  if (pos < n_rows) {
+    const int32_t doc = rows[pos];
+    if ((uint32_t)doc >= (uint32_t)ndocs) {  // k_compact ran out of room and left the row unwritten
+      atomicOr(err, kMetaErrUnformattable);
+    } else {
+      int32_t tok[kMaxMetaTokens];
+      for (int t = 0; t < kMaxMetaTokens; ++t) tok[t] = (t < mp->n_tokens && pos < nk) ? tk.p[t][pos] : -1;
+      MetaCountSink k;
+      if (!meta_row(*rp, *mp, recs.p, n, doc, pos < nk ? -1 : fail[doc], tok, k)) atomicOr(err, kMetaErrUnformattable);
+      len = k.n;
+    }
+  }
+  lens[pos] = len;
+  valid[pos] = len > 0;
+}
+
+// One lane per output row, one wave per workgroup. A lane formats its row into its own LDS slice
+// (65 dwords apart, so the lanes' byte stores fall into different banks), copying literals from an
+// LDS copy of the plan's pool; the rows of a wave are consecutive in the column, so the wave then
+// copies its byte range to HBM one aligned dword per lane and step (bytes at the ragged ends and
+// next to a long row one by one), finding the first byte's row by bisection of the wave's 65 row
+// starts. A row longer than a slice is written straight to the column by its lane and skipped by
+// the copy. The barriers, the starts and the copy loop sit outside the divergent formatting: every
+// lane takes part, and a lane without a row has length 0. moff: the column's offsets [ndocs + 1]
+// (the scan of k_meta_size's lengths).
+constexpr int kMetaSlice = 260;
+constexpr int kMetaWave = 64;
+constexpr int kMetaPoolLds = 4096;  // a larger pool is read from the plan in HBM
+
+__global__ __launch_bounds__(kMetaWave) void k_meta_write(const DevResolve* __restrict__ rp,
+                                                          const DevMetaPlan* __restrict__ mp, GateRecs recs,
+                                                          int32_t ndocs, const int32_t* __restrict__ fail,
+                                                          const int32_t* __restrict__ rows,
+                                                          const int64_t* __restrict__ sc, MetaTokens tk,
+                                                          const int64_t* __restrict__ moff, uint8_t* __restrict__ out,
+                                                          int64_t cap, int32_t* __restrict__ err) {
+  __shared__ uint32_t s_stage[kMetaWave * kMetaSlice / 4];
+  __shared__ uint32_t s_pool[kMetaPoolLds / 4];
+  __shared__ uint32_t s_start[kMetaWave + 1];
+  const int lane = threadIdx.x;
+  const int64_t n = ndocs;
+  const int64_t pos0 = (int64_t)blockIdx.x * kMetaWave, pos = pos0 + lane;
+  const int64_t total = moff[n];
+  if (total > cap || total < 0) {  // uniform over the grid: nothing is written
+    if (pos == 0) atomicOr(err, kMetaErrOverflow);
+    return;
+  }
+  const int64_t nk = sc[3 * n - 1];
+  const int64_t base = moff[pos0];
+  const int64_t o0 = moff[pos < n ? pos : n], o1 = moff[pos + 1 < n ? pos + 1 : n];
+  const uint32_t len = (uint32_t)(o1 - o0);
+  s_start[lane] = (uint32_t)(o0 - base);
+  if (lane == kMetaWave - 1) s_start[kMetaWave] = (uint32_t)(o1 - base);
+  {
+    const uint32_t* gp = (const uint32_t*)mp->pool;  // (the pool sits at a multiple of 4 in the plan)
+    const int pool_words = (mp->pool_used + 3) >> 2;
+    for (int i = lane; i < pool_words && i < kMetaPoolLds / 4; i += kMetaWave) s_pool[i] = gp[i];
+  }
+  const char* pool = mp->pool_used <= kMetaPoolLds ? (const char*)s_pool : mp->pool;
+  __syncthreads();
+  char* stage = (char*)s_stage + lane * kMetaSlice;
+  const int32_t doc = pos < n ? rows[pos] : -1;
+  if (len > 0 && (uint32_t)doc < (uint32_t)ndocs) {
+    int32_t tok[kMaxMetaTokens];
+    for (int t = 0; t < kMaxMetaTokens; ++t) tok[t] = (t < mp->n_tokens && pos < nk) ? tk.p[t][pos] : -1;
+    MetaWriteSink k(len <= (uint32_t)kMetaSlice ? stage : (char*)out + o0);
+    (void)meta_row(*rp, *mp, recs.p, n, doc, pos < nk ? -1 : fail[doc], tok, k, pool);
+  }
+  __syncthreads();
+  // unit u = the aligned dword of `out` that holds the wave's bytes [4u - mis, 4u - mis + 4)
+  const uint32_t w_bytes = s_start[kMetaWave];
+  uint8_t* gout = out + base;
+  const uint32_t mis = (uint32_t)((uintptr_t)gout & 3u);
+  const uint32_t n_units = (w_bytes + mis + 3) >> 2;
+  const uint8_t* stage8 = (const uint8_t*)s_stage;
+  for (uint32_t u = lane; u < n_units; u += kMetaWave) {
+    const int32_t j0 = (int32_t)(4 * u) - (int32_t)mis;
+    const uint32_t ja = j0 < 0 ? 0u : (uint32_t)j0;
+    const uint32_t jb = (uint32_t)(j0 + 4) < w_bytes ? (uint32_t)(j0 + 4) : w_bytes;
+    int r = 0, hi = kMetaWave - 1;  // the last row with start <= ja (rows of length 0 share a start)
+    while (r < hi) {
+      const int mid = (r + hi + 1) >> 1;
+      if (s_start[mid] <= ja) r = mid;
+      else hi = mid - 1;
+    }
+    uint32_t word = 0, have = 0;
+    for (uint32_t j = ja; j < jb; ++j) {
+      while (s_start[r + 1] <= j) ++r;  // j < w_bytes = s_start[64]: r stays <= 63
+      if (s_start[r + 1] - s_start[r] <= (uint32_t)kMetaSlice) {
+        const uint32_t sh = (uint32_t)((int32_t)j - j0);
+        word |= (uint32_t)stage8[r * kMetaSlice + (j - s_start[r])] << (8 * sh);
+        have |= 1u << sh;
+      }
+    }
+    if (have == 0xFu) {
+      *(uint32_t*)(gout + j0) = word;
+    } else {
+      for (uint32_t b = 0; b < 4; ++b)
+        if (have >> b & 1) gout[j0 + (int32_t)b] = (uint8_t)(word >> (8 * b));
+    }
+  }
+}
+
 }  // namespace
 
 // CUs of the current device (queried once; thread-safe static initialisation)
@@ -2416,6 +2539,41 @@ int tb_resolve(hipStream_t stream, const void* rp, const int64_t* const* recs, i
 
 size_t tb_sizeof_resolve() { return sizeof(DevResolve); }
 
+// K18 after tb_resolve (and the token counts) on `stream`: k_meta_size, the scan of the lengths
+// into off[1 .. ndocs] (off[0] = 0), k_meta_write. fail / rows / sc: tb_resolve's outputs; toks:
+// ntoks k_bpe_count result arrays (= the plan's n_tokens). lens: ndocs int64 scratch, off:
+// ndocs + 1, valid: ndocs, out: cap bytes (the plan's row_cap * ndocs); err: kMetaErr* bits.
+struct TbMetaOut {
+  int64_t *lens, *off;
+  uint8_t *valid, *out;
+  int64_t cap;
+  int32_t* err;
+};
+size_t tb_sizeof_meta_out() { return sizeof(TbMetaOut); }
+size_t tb_sizeof_meta_plan() { return sizeof(DevMetaPlan); }
+
+int tb_meta_format(hipStream_t stream, const void* rp, const void* mp, const int64_t* const* recs, int32_t nrecs,
+                   int32_t ndocs, const int32_t* fail, const int32_t* rows, const int64_t* sc,
+                   const int32_t* const* toks, int32_t ntoks, const TbMetaOut* o) {
+  if (ndocs <= 0) return 0;
+  if (nrecs < 0 || nrecs > kMaxGateSteps || ntoks < 0 || ntoks > kMaxMetaTokens || !o->lens || !o->off || !o->valid ||
+      !o->out || !o->err || o->cap < 0)
+    return (int)hipErrorInvalidValue;
+  GateRecs r{};
+  for (int i = 0; i < nrecs; ++i) r.p[i] = recs[i];
+  MetaTokens tk{};
+  for (int i = 0; i < ntoks; ++i) tk.p[i] = toks[i];
+  hipLaunchKernelGGL(k_meta_size, dim3((ndocs + 255) / 256), dim3(256), 0, stream, (const DevResolve*)rp,
+                     (const DevMetaPlan*)mp, r, ndocs, fail, rows, sc, tk, o->lens, o->valid, o->err);
+  (void)hipMemsetAsync(o->off, 0, sizeof(int64_t), stream);
+  const int rc = tb_scan_strided_i64(stream, o->lens, 1, ndocs, o->off + 1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_meta_write, dim3((ndocs + kMetaWave - 1) / kMetaWave), dim3(kMetaWave), 0, stream,
+                     (const DevResolve*)rp, (const DevMetaPlan*)mp, r, ndocs, fail, rows, sc, tk,
+                     (const int64_t*)o->off, o->out, o->cap, o->err);
+  return (int)hipGetLastError();
+}
+
 
 int tb_pow_table(hipStream_t stream, uint64_t* pw, uint32_t n) {
   hipLaunchKernelGGL(k_pow_table, dim3((n + 256) / 256), dim3(256), 0, stream, pw, n);
@@ -2425,7 +2583,7 @@ int tb_pow_table(hipStream_t stream, uint64_t* pw, uint32_t n) {
 int tb_phase_slots() { return kPhaseSlots; }
 int tb_stage_waves() { return TB_STAGE_WPE; }  // waves per SIMD the wave stage kernel is built for
 
-int tb_abi_version() { return 26; }
+int tb_abi_version() { return 27; }
 size_t tb_sizeof_plan() { return sizeof(DevPlan); }
 size_t tb_sizeof_stage() { return sizeof(DevStage); }
 size_t tb_sizeof_c4() { return sizeof(DevC4); }

@@ -7,9 +7,11 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 
 #include "../common/docproc.h"
+#include "../common/metafmt.h"
 
 namespace tb {
 
@@ -297,6 +299,209 @@ void resolve_host(const DevResolve& rp, const std::vector<const int64_t*>& recs,
       out.append(vdata[v] + voff[v][doc], (size_t)(voff[v][doc + 1] - voff[v][doc]));
     }
   out_off[pos] = (int64_t)out.size();
+}
+
+// ---- K18: the metadata plan (csrc/common/metafmt.h) -----------------------------------------
+namespace {
+struct MetaPool {
+  DevMetaPlan& mp;
+  // raw text, escaped as json_escape_append would inside a string value (no surrounding quotes)
+  static std::string esc(std::string_view s) {
+    std::string q;
+    json_escape_append(q, s);
+    return q.substr(1, q.size() - 2);
+  }
+  MetaLit add(const std::string& bytes) {
+    if ((size_t)mp.pool_used + bytes.size() > (size_t)kMetaPoolBytes)
+      throw std::invalid_argument("meta plan: literal pool full");
+    MetaLit l{(uint16_t)mp.pool_used, (uint16_t)bytes.size()};
+    std::memcpy(mp.pool + mp.pool_used, bytes.data(), bytes.size());
+    mp.pool_used += (int32_t)bytes.size();
+    return l;
+  }
+};
+std::string member_open(std::string_view key) { return "\"" + MetaPool::esc(key) + "\":\""; }
+std::string member(std::string_view key, std::string_view value) {
+  return member_open(key) + MetaPool::esc(value) + "\"";
+}
+std::string f2(double v) { return fmt_fixed(v, 2); }
+std::string f4(double v) { return fmt_fixed(v, 4); }
+std::string i64s(int64_t v) {
+  std::string s;
+  append_i64(s, v);
+  return s;
+}
+}  // namespace
+
+DevMetaPlan build_meta_plan(const std::vector<StepCfg>& steps, const DevResolve& rp, int n_tokens, int row_cap) {
+  // the fast_meta condition of BatchState::assemble (steps of distinct kinds never write the same
+  // key, so a row is the plain concatenation of its steps' members), and no host-decided step
+  for (size_t a = 0; a < steps.size(); ++a) {
+    if (steps[a].kind == StepKind::C4BadWords) throw std::invalid_argument("meta plan: C4BadWords is decided on the host");
+    for (size_t b = a + 1; b < steps.size(); ++b)
+      if (steps[a].kind == steps[b].kind) throw std::invalid_argument("meta plan: two steps of one kind");
+  }
+  size_t n_need = steps.size();
+  while (n_need > 0 && steps[n_need - 1].kind == StepKind::TokenCounter) --n_need;
+  if (n_tokens != (int)(steps.size() - n_need) || n_tokens > kMaxMetaTokens || (size_t)rp.gate.n_steps != n_need)
+    throw std::invalid_argument("meta plan: steps do not match the resolve plan");
+  auto plan = std::make_unique<DevMetaPlan>();
+  DevMetaPlan& mp = *plan;
+  std::memset(&mp, 0, sizeof(mp));
+  MetaPool pool{mp};
+  mp.n_steps = rp.gate.n_steps;
+  mp.n_tokens = n_tokens;
+  mp.token = pool.add(member_open("token_count"));
+  // Longest row: per step the longer of its passing members and its failing members with every
+  // reason firing and every dynamic value at its longest (24 bytes: i64, or a fixed-point value
+  // below 10^14 with its sign and decimals); the confidence takes up to 19.
+  constexpr size_t kDyn = 24;
+  size_t worst = 2 + (size_t)n_tokens * (1 + mp.token.len + kDyn + 1);
+  for (int k = 0; k < rp.gate.n_steps; ++k) {
+    const int si = rp.step_index[k];
+    if (si < 0 || si >= (int)steps.size()) throw std::invalid_argument("meta plan: step index");
+    const StepCfg& c = steps[si];
+    MetaLit* L = mp.steps[k].lit;
+    auto reason = [&](int r, const std::string& pre, const std::string& suf) {
+      if (ML_REASON0 + 2 * r + 1 >= kMaxMetaLits) throw std::invalid_argument("meta plan: too many reasons");
+      L[ML_REASON0 + 2 * r] = pool.add(MetaPool::esc(pre));
+      L[ML_REASON0 + 2 * r + 1] = pool.add(MetaPool::esc(suf));
+    };
+    auto multi_head = [&](std::string_view status_key, std::string_view reasons_key) {
+      L[ML_PASSED] = pool.add(member(status_key, "passed"));
+      L[ML_HEAD] = pool.add(member(status_key, "filtered") + "," + member_open(reasons_key));
+    };
+    int n_reasons = 0;
+    switch (c.kind) {
+      case StepKind::GopherQuality: {
+        multi_head("gopher_quality_filter_status", "gopher_quality_filter_reasons");
+        const int64_t minw = c.min_doc_words.value_or(0), maxw = c.max_doc_words.value_or(0);
+        const int64_t mins = c.min_stop_words.value_or(0);
+        const double mina = c.min_avg_word_length.value_or(0), maxa = c.max_avg_word_length.value_or(0);
+        const double sym = c.max_symbol_word_ratio.value_or(0);
+        reason(MQ_SHORT, "gopher_short_doc (", " non-symbol words, required " + i64s(minw) + ")");
+        reason(MQ_LONG, "gopher_long_doc (", " non-symbol words, max " + i64s(maxw) + ")");
+        reason(MQ_BELOW_AVG, "gopher_below_avg_threshold (avg len ", ", required " + f2(mina) + ")");
+        L[ML_X0] = pool.add(MetaPool::esc(", required " + f2(mina) + (mina > 0.0 ? " - 0 non-symbol words" : "") + ")"));
+        reason(MQ_ABOVE_AVG, "gopher_above_avg_threshold (avg len ", ", max " + f2(maxa) + ")");
+        reason(MQ_HASHES, "gopher_too_many_hashes (ratio ", ", max " + f2(sym) + ")");
+        reason(MQ_ELLIPSIS, "gopher_too_many_ellipsis_units (ratio ", ", max " + f2(sym) + ")");
+        reason(MQ_BULLETS, "gopher_too_many_bullets (ratio ", ", max " + f2(c.max_bullet_lines_ratio.value_or(0)) + ")");
+        reason(MQ_ELL_LINES, "gopher_too_many_end_ellipsis_lines (ratio ",
+               ", max " + f2(c.max_ellipsis_lines_ratio.value_or(0)) + ")");
+        reason(MQ_ALPHA, "gopher_below_alpha_threshold (alpha ratio ",
+               ", required min " + f2(c.max_non_alpha_words_ratio.value_or(0)) + ")");
+        reason(MQ_STOP, "gopher_too_few_stop_words (found ", ", required " + i64s(mins) + ")");
+        n_reasons = 10;
+        break;
+      }
+      case StepKind::GopherRepetition: {
+        multi_head("gopher_repetition_filter_status", "gopher_repetition_filter_reasons");
+        L[ML_X0] = pool.add(member("gopher_repetition_filter_status", "filtered") + "," +
+                            member("gopher_repetition_filter_reason", "skipping empty content"));
+        reason(0, "dup_para_frac (ratio ", ", max " + f2(c.dup_para_frac.value_or(0)) + ")");
+        reason(1, "dup_para_char_frac (ratio ", ", max " + f2(c.dup_para_char_frac.value_or(0)) + ")");
+        reason(2, "dup_line_frac (ratio ", ", max " + f2(c.dup_line_frac.value_or(0)) + ")");
+        reason(3, "dup_line_char_frac (ratio ", ", max " + f2(c.dup_line_char_frac.value_or(0)) + ")");
+        int r = 4;
+        for (auto& e : c.top_n_grams) reason(r++, "top_" + i64s(e.first) + "_gram (ratio ", ", max " + f2(e.second) + ")");
+        for (auto& e : c.dup_n_grams)
+          reason(r++, "duplicated_" + i64s(e.first) + "_n_grams (ratio ", ", max " + f2(e.second) + ")");
+        n_reasons = r;
+        break;
+      }
+      case StepKind::C4Quality: {
+        multi_head("c4_filter_status", "c4_filter_reasons");
+        L[ML_X0] = pool.add(MetaPool::esc("lorem_ipsum"));
+        L[ML_X1] = pool.add(MetaPool::esc("curly_bracket"));
+        reason(0, "too_few_sentences (found ", ", required " + i64s(c.min_num_sentences) + ")");
+        L[MC_LINE0 + 0] = pool.add("," + member_open("line-filter-too_long_word"));
+        L[MC_LINE0 + 1] = pool.add("," + member_open("line-filter-no_terminal_punc"));
+        L[MC_LINE0 + 2] = pool.add("," + member_open("line-filter-too_few_words"));
+        n_reasons = 5;  // (the line-filter members count as reasons for the bound)
+        break;
+      }
+      case StepKind::FineWebQuality: {
+        const std::string head = member("fineweb_filter_status", "filtered") + "," + member_open("fineweb_filter_reason");
+        L[ML_X0] = pool.add(head + MetaPool::esc("empty document") + "\"");
+        L[ML_X1] = pool.add(head + MetaPool::esc("list_ratio_no_words (newlines present but no words)") + "\"");
+        auto fw = [&](int r, const std::string& pre, const std::string& suf) {
+          L[ML_REASON0 + 2 * r] = pool.add(head + MetaPool::esc(pre));
+          L[ML_REASON0 + 2 * r + 1] = pool.add(MetaPool::esc(suf) + "\"");
+        };
+        fw(0, "line_punct_ratio: ", " < threshold " + f4(c.line_punct_thr) + " (exclude_zero: " +
+                                        (c.line_punct_exclude_zero ? "true" : "false") + ")");
+        fw(1, "short_line_ratio: ", " > threshold " + f4(c.short_line_thr));
+        fw(2, "char_dup_ratio: ", " > threshold " + f4(c.char_duplicates_ratio));
+        fw(3, "list_ratio: ", " > threshold " + f4(c.new_line_ratio));
+        n_reasons = 1;
+        break;
+      }
+      case StepKind::LanguageDetection:
+        for (int l = 0; l < kMetaLangs; ++l)
+          L[ML_X0 + l] = pool.add(member("Detected language", kLangNames[l]) + "," +
+                                  member_open("Detected language confidence"));
+        n_reasons = 0;
+        break;
+      default:
+        throw std::invalid_argument("meta plan: step without a device decision");
+    }
+    size_t fail_len = L[ML_HEAD].len + 1, longest = 0;
+    for (int j = ML_X0; j < kMaxMetaLits; ++j) longest = std::max<size_t>(longest, L[j].len);
+    if (c.kind == StepKind::FineWebQuality || c.kind == StepKind::LanguageDetection)
+      fail_len = 2 * longest + kDyn + 1;
+    else
+      for (int r = 0; r < n_reasons; ++r)
+        fail_len += 2 + L[ML_REASON0 + 2 * r].len + L[ML_REASON0 + 2 * r + 1].len + kDyn + 1;
+    fail_len = std::max(fail_len, longest + L[ML_HEAD].len + 32);
+    worst += 1 + std::max<size_t>(L[ML_PASSED].len, fail_len);
+  }
+  // Output capacity: the column buffer holds row_cap bytes per output row on average. The longest
+  // possible row bounds it; past 512 bytes the bound is not worth its HBM and D2H (default
+  // pipeline: ~1.9 KB with every reason of every step firing, against ~150 bytes for a typical
+  // CommonCrawl row), so 512 it is, and a batch that needs more sets the error word and is
+  // assembled on the host. row_cap > 0 overrides it (tests force the overflow that way).
+  mp.row_cap = row_cap > 0 ? row_cap : (int32_t)std::min<size_t>(worst, 512);
+  return mp;
+}
+
+void meta_format_host(const DevResolve& rp, const DevMetaPlan& mp, const std::vector<const int64_t*>& recs,
+                      int64_t ndocs, const int32_t* fail, const int32_t* rows, int64_t nk, int64_t nx,
+                      const std::vector<const int32_t*>& tokens, std::string& out, std::vector<int64_t>& off,
+                      std::vector<uint8_t>& valid, int32_t& err) {
+  if ((int)tokens.size() != mp.n_tokens) throw std::runtime_error("meta: token arrays");
+  for (int s = 0; s < rp.gate.n_steps; ++s)
+    if (rp.gate.steps[s].slot < 0 || rp.gate.steps[s].slot >= (int)recs.size())
+      throw std::runtime_error("meta record slot out of range");
+  const int64_t n_rows = nk + nx;
+  err = 0;
+  off.assign(n_rows + 1, 0);
+  valid.assign(n_rows, 0);
+  auto tok_of = [&](int64_t pos, int32_t* tok) {
+    for (int t = 0; t < mp.n_tokens; ++t) tok[t] = pos < nk ? tokens[t][pos] : -1;
+  };
+  for (int64_t pos = 0; pos < n_rows; ++pos) {  // k_meta_size
+    int32_t tok[kMaxMetaTokens];
+    tok_of(pos, tok);
+    MetaCountSink k;
+    if (!meta_row(rp, mp, recs.data(), ndocs, rows[pos], pos < nk ? -1 : fail[rows[pos]], tok, k))
+      err |= kMetaErrUnformattable;
+    off[pos + 1] = off[pos] + k.n;  // the scan
+    valid[pos] = k.n > 0;
+  }
+  out.clear();
+  if (off[n_rows] > (int64_t)mp.row_cap * ndocs) {  // k_meta_write
+    err |= kMetaErrOverflow;
+    return;
+  }
+  out.resize((size_t)off[n_rows]);
+  for (int64_t pos = 0; pos < n_rows; ++pos) {
+    int32_t tok[kMaxMetaTokens];
+    tok_of(pos, tok);
+    MetaWriteSink k(out.data() + off[pos]);
+    meta_row(rp, mp, recs.data(), ndocs, rows[pos], pos < nk ? -1 : fail[rows[pos]], tok, k);
+    if ((int64_t)k.n != off[pos + 1] - off[pos]) throw std::runtime_error("meta: size and write passes disagree");
+  }
 }
 
 std::vector<uint64_t> pow_table(uint32_t n) {

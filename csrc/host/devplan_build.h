@@ -5,6 +5,7 @@
 
 #include "../common/devplan.h"
 #include "../common/gate.h"
+#include "../common/metafmt.h"
 #include "filters.h"
 #include "pipeline.h"
 
@@ -35,6 +36,18 @@ void resolve_host(const DevResolve& rp, const std::vector<const int64_t*>& recs,
                   const uint32_t* flags, const std::vector<const char*>& vdata,
                   const std::vector<const int64_t*>& voff, std::vector<int32_t>& fail, std::vector<uint8_t>& status,
                   std::string& out, std::vector<int64_t>& out_off, std::vector<int32_t>& rows);
+// K18 metadata plan (csrc/common/metafmt.h) for the pipeline `rp` resolves: n_tokens trailing
+// TokenCounter steps whose counts come from the device; row_cap > 0 overrides the output capacity
+// per row (tests). Throws std::invalid_argument when the rows cannot be formatted on the device
+// (a C4BadWords step, two steps of one kind, a literal pool that does not fit).
+DevMetaPlan build_meta_plan(const std::vector<StepCfg>& steps, const DevResolve& rp, int n_tokens, int row_cap = 0);
+// Host run of k_meta_size + scan + k_meta_write (same per-row function): rows = r_rows of the
+// resolve (nk kept, then nx excluded), tokens[t][k] = device count of kept output k. err: the
+// kernels' error word (kMetaErr*); on overflow nothing is written.
+void meta_format_host(const DevResolve& rp, const DevMetaPlan& mp, const std::vector<const int64_t*>& recs,
+                      int64_t ndocs, const int32_t* fail, const int32_t* rows, int64_t nk, int64_t nx,
+                      const std::vector<const int32_t*>& tokens, std::string& out, std::vector<int64_t>& off,
+                      std::vector<uint8_t>& valid, int32_t& err);
 std::vector<uint64_t> pow_table(uint32_t n);  // B^0..B^n followed by B^-0..B^-n
 
 void emulate_stage(const std::vector<StepCfg>& steps, const std::vector<int>& idx, int64_t ndocs,

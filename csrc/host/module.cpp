@@ -781,7 +781,26 @@ PYBIND11_MODULE(_tbhost, m) {
                                               to_numpy(std::move(mv)));
         return py::make_tuple(raw_to_numpy(td), to_numpy(std::move(to)), raw_to_numpy(md),
                               to_numpy(std::move(mo)), to_numpy(std::move(mv)));
-      }, py::arg("idx"), py::arg("with_text") = true);
+      }, py::arg("idx"), py::arg("with_text") = true)
+      .def("splice_meta", [](PyBatch& b, py::array_t<int64_t, py::array::c_style> idx,
+                             py::array_t<uint8_t, py::array::c_style> dev, py::array_t<int64_t, py::array::c_style> dev_off,
+                             py::array_t<uint8_t, py::array::c_style> dev_valid) -> py::tuple {
+        const int64_t m = (int64_t)idx.size();
+        if ((int64_t)dev_off.size() != m + 1 || (int64_t)dev_valid.size() != m ||
+            (m > 0 && (dev_off.data()[0] < 0 || dev_off.data()[m] > (int64_t)dev.size())))
+          throw std::invalid_argument("splice_meta: device column shapes");
+        for (int64_t k = 0; k < m; ++k)
+          if (dev_off.data()[k + 1] < dev_off.data()[k]) throw std::invalid_argument("splice_meta: offsets");
+        std::vector<int64_t> iv(idx.data(), idx.data() + idx.size());
+        RawBuf md;
+        std::vector<int64_t> mo;
+        std::vector<uint8_t> mv;
+        {
+          py::gil_scoped_release nogil;
+          b.st->splice_meta(iv, (const char*)dev.data(), dev_off.data(), dev_valid.data(), md, mo, mv);
+        }
+        return py::make_tuple(raw_to_numpy(md), to_numpy(std::move(mo)), to_numpy(std::move(mv)));
+      });
 
   // ---- device plan building + host emulation of the device algorithms ----
   m.def("device_supported", [](const StepCfg& c) {
@@ -860,6 +879,61 @@ PYBIND11_MODULE(_tbhost, m) {
     }
     return py::make_tuple(to_numpy(std::move(fail)), to_numpy(std::move(status)), str_to_numpy(std::move(out)),
                           to_numpy(std::move(out_off)), to_numpy(std::move(rows)));
+  });
+  // ---- K18: metadata plan + host run of k_meta_size / k_meta_write (csrc/common/metafmt.h) ----
+  m.attr("SIZEOF_DEV_META_PLAN") = sizeof(DevMetaPlan);
+  m.attr("META_ERR_OVERFLOW") = kMetaErrOverflow;
+  m.attr("META_ERR_UNFORMATTABLE") = kMetaErrUnformattable;
+  m.def("build_meta_plan", [](const std::vector<StepCfg>& steps, const py::bytes& resolve, int n_tokens, int row_cap) {
+    std::string bs = resolve;
+    if (bs.size() != sizeof(DevResolve)) throw std::runtime_error("bad resolve blob");
+    DevResolve rp;
+    std::memcpy(&rp, bs.data(), sizeof(rp));
+    auto mp = std::make_unique<DevMetaPlan>(build_meta_plan(steps, rp, n_tokens, row_cap));
+    return py::bytes((const char*)mp.get(), sizeof(DevMetaPlan));
+  }, py::arg("steps"), py::arg("resolve"), py::arg("n_tokens") = 0, py::arg("row_cap") = 0);
+  m.def("meta_plan_row_cap", [](const py::bytes& meta) {
+    std::string ms = meta;
+    if (ms.size() != sizeof(DevMetaPlan)) throw std::runtime_error("bad meta plan blob");
+    return ((const DevMetaPlan*)ms.data())->row_cap;
+  });
+  m.def("meta_format_host", [](const py::bytes& resolve, const py::bytes& meta,
+                               const std::vector<py::array_t<int64_t, py::array::c_style>>& recs, int64_t ndocs,
+                               py::array_t<int32_t, py::array::c_style> fail,
+                               py::array_t<int32_t, py::array::c_style> rows, int64_t nk, int64_t nx,
+                               const std::vector<py::array_t<int32_t, py::array::c_style>>& tokens) {
+    std::string bs = resolve, ms = meta;
+    if (bs.size() != sizeof(DevResolve) || ms.size() != sizeof(DevMetaPlan)) throw std::runtime_error("bad plan blob");
+    DevResolve rp;
+    std::memcpy(&rp, bs.data(), sizeof(rp));
+    auto mp = std::make_unique<DevMetaPlan>();
+    std::memcpy(mp.get(), ms.data(), sizeof(DevMetaPlan));
+    if (nk < 0 || nx < 0 || nk + nx > ndocs || (int64_t)fail.size() < ndocs || (int64_t)rows.size() < nk + nx)
+      throw std::runtime_error("meta: operand shapes");
+    for (py::ssize_t k = 0; k < nk + nx; ++k)
+      if (rows.data()[k] < 0 || rows.data()[k] >= ndocs) throw std::runtime_error("meta: row out of range");
+    for (int s = 0; s < rp.gate.n_steps; ++s) {
+      const DevGateStep& st = rp.gate.steps[s];
+      if (st.slot < 0 || st.slot >= (int)recs.size() ||
+          (int64_t)recs[st.slot].size() < ((int64_t)st.prefix + st.width) * ndocs)
+        throw std::runtime_error("meta record buffer too short");
+    }
+    std::vector<const int64_t*> rp_ptrs;
+    for (auto& r : recs) rp_ptrs.push_back(r.data());
+    std::vector<const int32_t*> tp;
+    for (auto& t : tokens) {
+      if ((int64_t)t.size() < nk) throw std::runtime_error("meta: token array too short");
+      tp.push_back(t.data());
+    }
+    std::string out;
+    std::vector<int64_t> off;
+    std::vector<uint8_t> valid;
+    int32_t err = 0;
+    {
+      py::gil_scoped_release nogil;
+      meta_format_host(rp, *mp, rp_ptrs, ndocs, fail.data(), rows.data(), nk, nx, tp, out, off, valid, err);
+    }
+    return py::make_tuple(str_to_numpy(std::move(out)), to_numpy(std::move(off)), to_numpy(std::move(valid)), (int)err);
   });
   m.def("stage_layout", [](const py::bytes& b) {
     std::string s = b;

@@ -1001,4 +1001,82 @@ void BatchState::assemble(const std::vector<int64_t>& idx, RawBuf& text_data, st
   for (auto& p : mparts) give_charbuf(std::move(p));
 }
 
+void BatchState::splice_meta(const std::vector<int64_t>& idx, const char* dev, const int64_t* dev_off,
+                             const uint8_t* dev_valid, RawBuf& meta_data, std::vector<int64_t>& meta_off,
+                             std::vector<uint8_t>& meta_valid) const {
+  PoolTag pool_tag("assemble");
+  const int64_t m = (int64_t)idx.size();
+  // per row: 0 the device row, 1 canonical input + device members, 2 the general path
+  std::vector<uint8_t> how(m, 0);
+  std::vector<std::string_view> inner(m);
+  meta_off.assign(m + 1, 0);
+  meta_valid.assign(m, 0);
+  parallel_for(m, nthreads_, [&](int64_t a, int64_t b) {
+    for (int64_t k = a; k < b; ++k) {
+      const int64_t i = idx[k];
+      const int64_t dl = dev_valid[k] ? dev_off[k + 1] - dev_off[k] : 0;
+      if (!meta_data_ || (meta_valid_ && !meta_valid_[i])) {
+        meta_off[k + 1] = dl;
+        meta_valid[k] = dl > 0;
+        continue;
+      }
+      const std::string_view raw(meta_data_ + meta_off_[i], (size_t)(meta_off_[i + 1] - meta_off_[i]));
+      if (!canonical_meta(raw, inner[k])) {
+        how[k] = 2;
+        continue;
+      }
+      how[k] = 1;
+      // '{' inner [',' the device members] '}'; nothing at all makes a null row
+      const int64_t dm = dl >= 2 ? dl - 2 : 0;
+      if (inner[k].empty() && dm == 0) continue;
+      meta_off[k + 1] = 2 + (int64_t)inner[k].size() + (inner[k].empty() || dm == 0 ? 0 : 1) + dm;
+      meta_valid[k] = 1;
+    }
+  });
+  std::vector<int64_t> gen_idx, gen_pos;
+  for (int64_t k = 0; k < m; ++k)
+    if (how[k] == 2) {
+      gen_idx.push_back(idx[k]);
+      gen_pos.push_back(k);
+    }
+  RawBuf gtd, gmd;
+  std::vector<int64_t> gto, gmo;
+  std::vector<uint8_t> gmv;
+  if (!gen_idx.empty()) {
+    assemble(gen_idx, gtd, gto, gmd, gmo, gmv, false);
+    for (size_t g = 0; g < gen_idx.size(); ++g) {
+      meta_off[gen_pos[g] + 1] = gmo[g + 1] - gmo[g];
+      meta_valid[gen_pos[g]] = gmv[g];
+    }
+  }
+  for (int64_t k = 0; k < m; ++k) meta_off[k + 1] += meta_off[k];
+  meta_data.alloc((size_t)meta_off[m]);
+  std::vector<int64_t> gen_of(gen_idx.empty() ? 0 : m, -1);
+  for (size_t g = 0; g < gen_pos.size(); ++g) gen_of[gen_pos[g]] = (int64_t)g;
+  parallel_for(m, nthreads_, [&](int64_t a, int64_t b) {
+    for (int64_t k = a; k < b; ++k) {
+      char* o = meta_data.p + meta_off[k];
+      const int64_t len = meta_off[k + 1] - meta_off[k];
+      if (len == 0) continue;
+      if (how[k] == 0) {
+        std::memcpy(o, dev + dev_off[k], (size_t)len);
+      } else if (how[k] == 2) {
+        std::memcpy(o, gmd.p + gmo[gen_of[k]], (size_t)len);
+      } else {
+        const int64_t dl = dev_valid[k] ? dev_off[k + 1] - dev_off[k] : 0;
+        const int64_t dm = dl >= 2 ? dl - 2 : 0;
+        *o++ = '{';
+        std::memcpy(o, inner[k].data(), inner[k].size());
+        o += inner[k].size();
+        if (!inner[k].empty() && dm) *o++ = ',';
+        if (dm) std::memcpy(o, dev + dev_off[k] + 1, (size_t)dm);
+        o += dm;
+        *o = '}';
+      }
+    }
+  });
+  RawBuf::release(gmd.p, gmd.cap);
+  RawBuf::release(gtd.p, gtd.cap);
+}
+
 }  // namespace tb

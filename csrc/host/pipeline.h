@@ -172,6 +172,13 @@ class BatchState {
   void assemble(const std::vector<int64_t>& idx, RawBuf& text_data, std::vector<int64_t>& text_off,
                 RawBuf& meta_data, std::vector<int64_t>& meta_off, std::vector<uint8_t>& meta_valid,
                 bool with_text = true) const;
+  // Metadata column of documents idx from the device-formatted column (K18, csrc/common/metafmt.h:
+  // row k of dev / dev_off / dev_valid holds the steps' members of document idx[k]) merged with the
+  // input metadata, byte for byte what assemble(idx, ..., false) builds: a row without input
+  // metadata is the device row; canonical input (canonical_meta) is spliced in front of the
+  // device members; any other row goes through assemble's general path.
+  void splice_meta(const std::vector<int64_t>& idx, const char* dev, const int64_t* dev_off, const uint8_t* dev_valid,
+                   RawBuf& meta_data, std::vector<int64_t>& meta_off, std::vector<uint8_t>& meta_valid) const;
   int64_t meta_parse_failures() const { return meta_fail_.load(); }
 
  private:

@@ -28,7 +28,7 @@ _SZ = ctypes.c_size_t
 
 # Bumped with every change of an entry point's signature or of a launch struct's layout: a stale
 # libtbhip.so with an older argument list would otherwise be called with the wrong arguments.
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 def _ptr(t) -> Optional[int]:
@@ -85,9 +85,14 @@ class ResolveOut(ctypes.Structure):
                 ("out_off", _P), ("rows", _P), ("err", _P)]
 
 
+class MetaOut(ctypes.Structure):
+    """TbMetaOut: outputs and scratch of tb_meta_format (``cap``: bytes of ``out``)."""
+    _fields_ = [("lens", _P), ("off", _P), ("valid", _P), ("out", _P), ("cap", _I64), ("err", _P)]
+
+
 LAUNCH_STRUCTS = {Tables: "tb_sizeof_tables", Docs: "tb_sizeof_docs", Work: "tb_sizeof_work",
                   DictIn: "tb_sizeof_dict_in", DictLines: "tb_sizeof_dict_lines", BadWords: "tb_sizeof_badwords",
-                  ResolveOut: "tb_sizeof_resolve_out"}
+                  ResolveOut: "tb_sizeof_resolve_out", MetaOut: "tb_sizeof_meta_out"}
 
 _TAB, _DOCS, _WORK = ctypes.POINTER(Tables), ctypes.POINTER(Docs), ctypes.POINTER(Work)
 
@@ -115,6 +120,9 @@ _SIGS = {
     "tb_gate": [_P, _P, _P, _I32, _I32, _P, _P, _I32],
     # stream, rp, recs, nrecs, ndocs, flags, vb, vo, nver, outputs
     "tb_resolve": [_P, _P, _P, _I32, _I32, _P, _P, _P, _I32, ctypes.POINTER(ResolveOut)],
+    # stream, rp, mp, recs, nrecs, ndocs, fail, rows, sc, toks, ntoks, outputs
+    "tb_meta_format": [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, ctypes.POINTER(MetaOut)],
+    "tb_sizeof_meta_plan": [],
     "tb_pow_table": [_P, _P, _U32],
     "tb_html_sizes": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P],
     "tb_html_scatter": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P, _P],
@@ -205,7 +213,8 @@ class Kernels:
             raise DeviceError(f"libtbhip.so ABI {self.lib.tb_abi_version()} != {ABI_VERSION}; rebuild")
         if (self.lib.tb_sizeof_plan() != h.SIZEOF_DEV_PLAN or self.lib.tb_sizeof_stage() != h.SIZEOF_DEV_STAGE
                 or self.lib.tb_sizeof_gate() != h.SIZEOF_DEV_GATE
-                or self.lib.tb_sizeof_resolve() != h.SIZEOF_DEV_RESOLVE):
+                or self.lib.tb_sizeof_resolve() != h.SIZEOF_DEV_RESOLVE
+                or self.lib.tb_sizeof_meta_plan() != h.SIZEOF_DEV_META_PLAN):
             raise DeviceError("libtbhip.so and _tbhost disagree on the device plan layout; rebuild")
         self.sizeof_gr_export = int(self.lib.tb_sizeof_gr_export())
         if int(self.lib.tb_sizeof_pre_doc()) != PRE_DOC.itemsize:
@@ -441,3 +450,21 @@ class Kernels:
         rc = self.lib.tb_resolve(self.stream(), rp.data_ptr(), ra, len(recs), ndocs, flags.data_ptr(), vb, vo,
                                  len(versions), bufs)
         _check(rc, "tb_resolve")
+
+    def meta_format(self, rp, mp, recs, ndocs, fail, rows, sc, toks, lens, off, valid, out, err):
+        """K18: k_meta_size + scan + k_meta_write (see tb_meta_format) over tb_resolve's ``fail`` /
+        ``rows`` / ``sc``. ``toks``: the k_bpe_count result arrays of the plan's trailing
+        TokenCounter steps; ``lens`` [ndocs] scratch, ``off`` [ndocs + 1], ``valid`` [ndocs],
+        ``out`` the column bytes, ``err`` one zeroed int32 are the outputs."""
+        if len(recs) > 8 or len(toks) > 4:
+            raise DeviceError("meta_format: too many record buffers or token arrays")
+        if (fail.numel() < ndocs or rows.numel() < ndocs or sc.numel() < 4 * ndocs or lens.numel() < ndocs
+                or off.numel() < ndocs + 1 or valid.numel() < ndocs or err.numel() < 1
+                or any(t.numel() < ndocs for t in toks) or lens.dtype != np.int64 or off.dtype != np.int64
+                or fail.dtype != np.int32 or rows.dtype != np.int32 or sc.dtype != np.int64):
+            raise DeviceError("meta_format: operand shapes")
+        ra, ta = (ctypes.cast(_ptr_array8(x), ctypes.c_void_p) for x in (recs, toks))
+        bufs = MetaOut(lens.data_ptr(), off.data_ptr(), valid.data_ptr(), out.data_ptr(), out.numel(), err.data_ptr())
+        rc = self.lib.tb_meta_format(self.stream(), rp.data_ptr(), mp.data_ptr(), ra, len(recs), ndocs,
+                                     fail.data_ptr(), rows.data_ptr(), sc.data_ptr(), ta, len(toks), bufs)
+        _check(rc, "tb_meta_format")

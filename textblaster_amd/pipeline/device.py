@@ -70,6 +70,13 @@ class Resolved:
     # output k (k < number kept; -2: count it on the host)
     tokens: Optional[Dict[int, np.ndarray]] = None
 
+    # K18 (csrc/common/metafmt.h): the metadata column of the outputs above, formatted from the
+    # records — (bytes, int64 offsets over the nk + nx output rows, validity bytes) — and its error
+    # word (nonzero: overflow or an unformattable row, the host assembles the batch). None without
+    # a metadata plan (TB_TUNE device_meta=0, C4BadWords, two steps of one kind).
+    meta: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None
+    meta_err: int = 0
+
     # kept outputs a host step filtered afterwards (C4BadWords keep-fraction draws): bool over
     # the device's kept outputs; they move to the excluded side (Engine._device_resolve_agrees)
     moved: Optional[np.ndarray] = None
@@ -89,6 +96,16 @@ class Resolved:
         nk, _ = self.counts()
         dev = dev[:nk]
         return dev[~self.moved] if self.moved is not None else dev
+
+    def meta_parts(self):
+        """((bytes, offsets, validity) of the kept rows, the same of the excluded rows): views of
+        the device-formatted metadata column, or None when it cannot be used."""
+        if self.meta is None or self.meta_err or self.moved is not None:
+            return None
+        nk, nx = self.counts()
+        md, mo, mv = self.meta
+        kb, tot = int(mo[nk]), int(mo[nk + nx])
+        return ((md[:kb], mo[:nk + 1], mv[:nk]), (md[kb:tot], mo[nk:nk + nx + 1] - kb, mv[nk:nk + nx]))
 
     def parts(self, nthreads: int = 8):
         """([(kept rows, offsets, text)], [(excluded ...), ...]): views of the compacted buffer; with
@@ -211,6 +228,19 @@ def build_resolve(plan: ExecPlan, stage_layout, steps_native) -> Optional[bytes]
         return None
 
 
+def build_meta(plan: ExecPlan, steps_native, resolve_blob: Optional[bytes], n_device_tokens: int,
+               row_cap: int = 0) -> Optional[bytes]:
+    """K18 plan next to the K16 plan, or None: no resolve plan, a C4BadWords step, two steps of one
+    kind (the ``fast_meta`` condition of the host assembly), or a trailing TokenCounter the device
+    does not count. ``row_cap`` > 0 overrides the output capacity per row (tests)."""
+    if resolve_blob is None or n_device_tokens != len(trailing_token_counters(plan)):
+        return None
+    try:
+        return native.host().build_meta_plan(steps_native, resolve_blob, n_device_tokens, row_cap)
+    except ValueError:
+        return None
+
+
 def launch_order(lens: np.ndarray) -> np.ndarray:
     """Longest-first launch permutation (coarse 16-byte buckets: a stable radix sort on 16-bit
     keys instead of a comparison sort of int64 lengths)."""
@@ -281,8 +311,9 @@ class PendingBatch:
     the completion event and returns host views of the results."""
 
     def __init__(self, runner, ndocs, event, stage_recs, c4_recs, versions, flags, t_submit, keep, dead=None,
-                 resolved=None, bw=None):
+                 resolved=None, bw=None, meta=None):
         self.runner = runner
+        self._meta = meta
         self.ndocs = ndocs
         self.event = event
         self._stage_recs = stage_recs
@@ -331,6 +362,9 @@ class PendingBatch:
             fail, st, out, out_off, rows, err, ver = self._resolved[:7]
             tokens = {si: t for si, t in self._resolved[7:]} or None
             res = Resolved(fail, st, out, out_off, rows, int(err[0]), ver, tokens)
+            if self._meta is not None:
+                m_out, m_off, m_valid, m_err = self._meta
+                res.meta, res.meta_err = (m_out, m_off, m_valid), int(m_err[0])
         bwm = {i: m[:self.ndocs] for i, m in self._bw.items()} or None
         return DeviceResult(stage_recs, c4_recs, host_versions, fl, timings, dead, self.runner.pass_of_step, res, bwm)
 
@@ -434,8 +468,10 @@ class DeviceRunner:
 
     def __init__(self, steps_native, plan: ExecPlan, device, langid=None, max_batch_bytes: int = 384 << 20,
                  token_counters=None, slots: Optional[int] = None, host_threads: int = 8,
-                 tune: Optional[DeviceTuning] = None):
+                 tune: Optional[DeviceTuning] = None, meta_row_cap: int = 0):
         from ..ops import hiprt
+
+        self.meta_row_cap_override = int(meta_row_cap)  # K18 output capacity per row (tests; 0: the plan's)
 
         # operating points (pipeline/tuning.py: defaults with their A/B evidence, TB_TUNE overrides)
         self.tune = tu = (tune or tuning.from_env()).replace(slots=slots or None)
@@ -550,6 +586,13 @@ class DeviceRunner:
             self.bpe = []
             if self.resolve_t is not None and tu.device_tokens:
                 self.bpe = [(i, self.k.bpe_tables(sp)) for i, sp in (token_counters or [])]
+            # K18: the metadata column formatted on the device after K16 and the token counts
+            self.meta_t = None
+            if self.resolve_t is not None and tu.device_meta:
+                mblob = build_meta(plan, steps_native, blob, len(self.bpe), self.meta_row_cap_override)
+                if mblob is not None:
+                    self.meta_t = self._to_dev(mblob)
+                    self.meta_row_cap = int(h.meta_plan_row_cap(mblob))
             # B^k for the hashes, shared read-only by both slots: allocated once (longer spans
             # fall back to powmod61 in the kernels)
             with tracing.trace_range("tb.init.pow_table"):
@@ -1159,6 +1202,7 @@ class DeviceRunner:
         contents of kept / excluded documents compacted into one buffer (the host then only
         formats metadata), then the token counts of the kept outputs. Returns the device results
         to download, or None without a resolve plan."""
+        b.meta_d = None
         if self.resolve_t is None:
             return None
         rt, ndocs = self.rt, b.ndocs
@@ -1185,6 +1229,17 @@ class DeviceRunner:
                 self.k.bpe_count(tabs, r_out, r_off, r_sc[3 * ndocs - 1:3 * ndocs], ndocs, r_tok)
             b.keep.append(r_tok)
             res_d = res_d + ((si, r_tok),)
+        if self.meta_t is not None:
+            # K18 on the same stream: lengths, their scan, then the column bytes (row_cap bytes
+            # per output row on average; a batch past it sets the error word)
+            m_lens, m_off = rt.empty(ndocs, np.int64), rt.zeros(ndocs + 1, np.int64)
+            m_valid, m_err = rt.empty(ndocs, np.uint8), rt.zeros(1, np.int32)
+            m_out = rt.empty(max(self.meta_row_cap * ndocs, 1), np.uint8)
+            with self._ktimed(b.keep, "meta_format"):
+                self.k.meta_format(self.resolve_t, self.meta_t, recs, ndocs, r_fail, r_rows, r_sc,
+                                   [t for _, t in res_d[7:]], m_lens, m_off, m_valid, m_out, m_err)
+            b.keep += [m_lens, m_off, m_valid, m_out, m_err]
+            b.meta_d = (m_out, m_off, m_valid, m_err)
         return res_d
 
     def _download(self, b: "_Batch", res_d, t0: float, t1: float) -> PendingBatch:
@@ -1216,6 +1271,7 @@ class DeviceRunner:
             for ver in range(1, self.plan.n_versions):
                 vb, vo, _ = versions[ver]
                 h_versions[ver] = (d2h(vb), d2h(vo))
+        h_meta = tuple(d2h(t) for t in b.meta_d) if res_d is not None and b.meta_d is not None else None
         h_flags = d2h(b.flags)
         h_dead = d2h(b.dead) if b.dead is not None else None
         h_bw = {i: d2h(m) for i, m in b.bw_matched.items()}
@@ -1223,7 +1279,7 @@ class DeviceRunner:
         b.keep += [b.stage_recs, b.c4_recs, versions, b.flags, b.dead, b.ready, b.tails, done]
         t2 = time.perf_counter()
         return PendingBatch(self, b.ndocs, ev, h_stage, h_c4, h_versions, h_flags,
-                            {"stage_h2d": t1 - t0, "launch": t2 - t1}, b.keep, h_dead, h_res, h_bw)
+                            {"stage_h2d": t1 - t0, "launch": t2 - t1}, b.keep, h_dead, h_res, h_bw, h_meta)
 
     def run(self, data: np.ndarray, off: np.ndarray, bw: Optional[Dict[int, BwInput]] = None) -> DeviceResult:
         return self.submit(data, off, bw).wait()
@@ -1236,7 +1292,8 @@ class EmulatedRunner:
     the host side of the device pipeline."""
 
     def __init__(self, steps_native, plan: ExecPlan, langid=None, nthreads: int = 8, gating: Optional[bool] = None,
-                 gate_corrupt: int = 0, token_counters=None, tune: Optional[DeviceTuning] = None):
+                 gate_corrupt: int = 0, token_counters=None, tune: Optional[DeviceTuning] = None,
+                 meta_row_cap: int = 0):
         h = native.host()
         self.steps = steps_native
         self.plan = plan
@@ -1261,6 +1318,10 @@ class EmulatedRunner:
         if self.resolve_blob is not None and tu.device_tokens:
             self.bpe = list(token_counters or [])
         self.dict_marks = dict_marks_wanted(plan, steps_native, tu)
+        # K18 (host run of k_meta_size / k_meta_write over the same metafmt.h)
+        self.meta_blob = None
+        if tu.device_meta:
+            self.meta_blob = build_meta(plan, steps_native, self.resolve_blob, len(self.bpe), meta_row_cap)
 
     def run(self, data: np.ndarray, off: np.ndarray, bw: Optional[Dict[int, BwInput]] = None) -> DeviceResult:
         import time
@@ -1353,5 +1414,11 @@ class EmulatedRunner:
                 resolved.tokens = {
                     si: h.bpe_count(out, ko, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off,
                                     sp.post_add, self.nthreads) for si, sp in self.bpe}
+            if self.meta_blob is not None:
+                nk, nx = resolved.counts()
+                toks = [np.ascontiguousarray(resolved.tokens[si], dtype=np.int32) for si, _ in self.bpe]
+                md, mo, mv, merr = h.meta_format_host(self.resolve_blob, self.meta_blob, recs, ndocs, fail, rows, nk, nx,
+                                                      toks)
+                resolved.meta, resolved.meta_err = (md, mo, mv), int(merr)
         return DeviceResult(stage_recs, c4_recs, host_versions, flags, {"emulate": time.perf_counter() - t0}, dead,
                             self.pass_of_step, resolved, bwm or None)

@@ -116,7 +116,7 @@ class Engine:
                  keep_reasons: bool = False, tokenizer_file: Optional[str] = None,
                  fault_inject: Optional[str] = None, tokenizers=None, badwords=None,
                  max_batch_bytes: Optional[int] = None, slots: Optional[int] = None,
-                 tune: Optional[DeviceTuning] = None):
+                 tune: Optional[DeviceTuning] = None, meta_row_cap: int = 0):
         self.cfg = cfg
         self._cpu_engine = None
         self._n_submitted = 0
@@ -188,7 +188,8 @@ class Engine:
             from .device import EmulatedRunner
 
             self.device_runner = EmulatedRunner(self.steps, self.plan, self.langid, self.nthreads,
-                                                token_counters=token_counters, tune=self.tune)
+                                                token_counters=token_counters, tune=self.tune,
+                                                meta_row_cap=meta_row_cap)
         if backend == "cuda":
             for st in self.steps:
                 ok, why = self.h.device_supported(st)
@@ -199,7 +200,8 @@ class Engine:
             with tracing.trace_range("tb.init.device_runner"):
                 self.device_runner = DeviceRunner(self.steps, self.plan, device or "cuda", self.langid,
                                                   max_batch_bytes=self.max_batch_bytes, token_counters=token_counters,
-                                                  host_threads=self.nthreads, tune=self.tune)
+                                                  host_threads=self.nthreads, tune=self.tune,
+                                                  meta_row_cap=meta_row_cap)
 
     # ------------------------------------------------------------------------------------------
     def process(self, data: np.ndarray, off: np.ndarray, meta: Optional[Tuple] = None,
@@ -537,6 +539,7 @@ class Engine:
             if len(delegated):
                 bs.delegate(delegated)
             resolved = getattr(res, "resolved", None)
+            had_meta = resolved is not None and resolved.meta is not None
             vid = {0: 0}
             if resolved is not None:
                 # versions are registered (index v) only if the host assembles this batch
@@ -589,6 +592,11 @@ class Engine:
             if resolved is not None and not agreed and not self._device_resolve_agrees(bs, resolved):
                 resolved = None
                 self._register_versions(bs, res)
+            if had_meta and (resolved is None or resolved.meta_parts() is None):
+                # K18 ran but its column is not used: the host formats this batch's metadata
+                from ..utils import metrics
+
+                metrics.DEVICE_META_FALLBACK_TOTAL.inc()
             timings["resolve"] = time.perf_counter() - t1
         else:
             t1 = time.perf_counter()
@@ -596,7 +604,7 @@ class Engine:
             timings["cpu_pipeline"] = time.perf_counter() - t1
         t2 = time.perf_counter()
         with tracing.trace_range("tb.assemble"):
-            result = self._collect(bs, ndocs, timings, resolved)
+            result = self._collect(bs, ndocs, timings, resolved, has_meta=md is not None)
         if len(delegated):
             if self._async_delegation:
                 # recomputed on the delegation thread while the next batches are resolved; rows
@@ -849,7 +857,7 @@ class Engine:
             metrics.DEVICE_RESOLVE_FALLBACK_TOTAL.inc()
         return ok
 
-    def _collect(self, bs, ndocs: int, timings, resolved=None) -> BatchResult:
+    def _collect(self, bs, ndocs: int, timings, resolved=None, has_meta: bool = True) -> BatchResult:
         status = bs.status()
         fail = bs.fail_step()
         kept_rows = np.nonzero(status == 0)[0].astype(np.int64)
@@ -860,10 +868,18 @@ class Engine:
             # rows above; documents a host step filtered afterwards in a second excluded part);
             # only the metadata columns are built here
             sides = []
-            for side in resolved.parts(self.nthreads):
+            # K18: the metadata column came formatted from the device too (one part per side
+            # then); with input metadata the host splices it in front of the device members
+            dev_meta = resolved.meta_parts()
+            for k, side in enumerate(resolved.parts(self.nthreads)):
                 out = []
                 for rows, off, text in side:
-                    _, _, md, mo, mv = bs.assemble(rows, False)
+                    if dev_meta is None:
+                        _, _, md, mo, mv = bs.assemble(rows, False)
+                    elif has_meta:
+                        md, mo, mv = bs.splice_meta(rows, *(np.ascontiguousarray(a) for a in dev_meta[k]))
+                    else:
+                        md, mo, mv = dev_meta[k]
                     out.append(OutputPart(rows, text, off, md, mo, mv))
                 sides.append(out)
             kept_parts, excl_parts = sides

@@ -81,6 +81,10 @@ GATE_MISMATCH_DOCS_TOTAL = Counter("tb_gate_mismatch_docs_total",
 DEVICE_RESOLVE_FALLBACK_TOTAL = Counter("tb_device_resolve_fallback_total",
                                         "Batches whose device resolve/compaction (K16) disagreed with the host "
                                         "decisions and were assembled on the host (expected 0).", registry=REGISTRY)
+DEVICE_META_FALLBACK_TOTAL = Counter("tb_device_meta_fallback_total",
+                                     "Batches with a device-formatted metadata column (K18) that the host assembled "
+                                     "instead: an unformattable row, an overflow of the column buffer, or a K16 "
+                                     "fallback.", registry=REGISTRY)
 BPE_HOST_DOCS_TOTAL = Counter("tb_bpe_host_docs_total",
                               "Kept documents whose TokenCounter count the device handed to the host tokenizer "
                               "(added-token text or a pre-token over 64 bytes).", registry=REGISTRY)
