@@ -12,6 +12,8 @@
 #include "../common/badwords.h"
 #include "../common/bpe.h"
 #include "../common/bpe_classes.inc"
+#include "../common/wordpiece.h"
+#include "../common/wp_classes.inc"
 #include "../common/langid.h"
 #include "../common/ucd_tables.inc"
 #include "filters.h"
@@ -421,6 +423,102 @@ PYBIND11_MODULE(_tbhost, m) {
     return to_numpy(std::move(out));
   }, py::arg("data"), py::arg("off"), py::arg("byte_id"), py::arg("keys"), py::arg("vals"), py::arg("mask"),
         py::arg("added"), py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0);
+  // ---- WordPiece token counting (csrc/common/wordpiece.h; device kernel csrc/hip/wordpiece.hip) ----
+  m.def("wp_classes", []() {
+    std::vector<uint16_t> c1(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE1 + sizeof(TB_WP_CLS_STAGE1) / 2);
+    std::vector<uint8_t> c2(TB_WP_CLS_STAGE2, TB_WP_CLS_STAGE2 + sizeof(TB_WP_CLS_STAGE2));
+    return py::make_tuple(to_numpy(std::move(c1)), to_numpy(std::move(c2)));
+  });
+  m.def("wp_ascii", [](uint32_t shift) {
+    std::vector<uint64_t> a(4);
+    wp_ascii_classes(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE2, shift, a.data());
+    return to_numpy(std::move(a));
+  });
+  m.def("wp_build_table", [](py::array_t<uint8_t, py::array::c_style> pool, py::array_t<int64_t, py::array::c_style> off,
+                             py::array_t<uint8_t, py::array::c_style> cont) {
+    // pieces i = (cont[i], pool[off[i]:off[i + 1]]), distinct; open addressing, load <= 1/2.
+    // Returns the slots as uint64 pairs (WpSlot), the mask and the longest piece's bytes.
+    const size_t n = (size_t)cont.size();
+    if ((size_t)off.size() != n + 1 || n >= (1u << 30)) throw std::invalid_argument("wp_build_table: operand shapes");
+    const int64_t* o = off.data();
+    for (size_t i = 0; i < n; ++i)
+      if (o[i] < 0 || o[i + 1] <= o[i] || o[i + 1] > pool.size() || o[i + 1] - o[i] >= (1ll << 31) ||
+          o[i] >= (1ll << 32) || cont.data()[i] > 1)
+        throw std::invalid_argument("wp_build_table: piece offsets");
+    size_t cap = 16;
+    while (cap < 2 * n) cap <<= 1;
+    static_assert(sizeof(WpSlot) == 16, "WpSlot is two uint64");
+    std::vector<uint64_t> slots(2 * cap, kWpEmpty);
+    const uint64_t mask = cap - 1;
+    const int64_t longest =
+        wp_fill_slots(pool.data(), o, cont.data(), n, reinterpret_cast<WpSlot*>(slots.data()), mask);
+    return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)mask, longest);
+  });
+  m.def("wp_count", [](py::array_t<uint8_t, py::array::c_style> data, py::array_t<int64_t, py::array::c_style> off,
+                       py::array_t<uint64_t, py::array::c_style> slots, uint32_t mask,
+                       py::array_t<uint8_t, py::array::c_style> pool, uint32_t flags, uint32_t cls_shift,
+                       uint32_t self_bit, int32_t max_chars, int32_t longest,
+                       py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
+                       int nthreads, int64_t chunk) {
+    // host emulation of k_wp_count: per document the token count, or kBpeHost. chunk > 0: the
+    // wave split - the words starting in each chunk-byte range counted independently
+    // (wp_count_range), as the kernel's lanes do
+    if ((size_t)slots.size() != 2 * ((size_t)mask + 1) || added_off.size() > kBpeMaxAdded + 1 ||
+        (added_off.size() && added_off.back() > added.size()) || (cls_shift != 0 && cls_shift != 2) || longest < 1 ||
+        max_chars < 0)
+      throw std::invalid_argument("wp_count: operand shapes");
+    static_assert(sizeof(WpSlot) == 16, "WpSlot is two uint64");
+    const int64_t nd = off.size() - 1;
+    std::vector<int32_t> out(nd > 0 ? nd : 0);
+    DevWp T{};
+    T.slots = reinterpret_cast<const WpSlot*>(slots.data());
+    T.pool = pool.data();
+    T.cls1 = TB_WP_CLS_STAGE1;
+    T.cls2 = TB_WP_CLS_STAGE2;
+    T.added = added.data();
+    uint64_t asc[4];
+    wp_ascii_classes(T.cls1, T.cls2, cls_shift, asc);
+    T.asc0 = asc[0]; T.asc1 = asc[1]; T.asc2 = asc[2]; T.asc3 = asc[3];
+    T.mask = mask;
+    T.flags = flags;
+    T.cls_shift = cls_shift;
+    T.self_bit = self_bit;
+    T.max_chars = max_chars;
+    T.longest = longest;
+    T.post_add = post_add;
+    T.n_added = added_off.empty() ? 0 : (int32_t)added_off.size() - 1;
+    for (size_t i = 0; i < added_off.size(); ++i) T.added_off[i] = added_off[i];
+    const uint8_t* d = data.data();
+    const int64_t* o = off.data();
+    {
+      py::gil_scoped_release nogil;
+      const int nt = std::max(1, std::min<int>(nthreads, (int)(nd / 256) + 1));
+      std::vector<std::thread> th;
+      for (int t = 0; t < nt; ++t)
+        th.emplace_back([&, t]() {
+          for (int64_t k = t; k < nd; k += nt) {
+            const uint8_t* b = d + o[k];
+            const int64_t n = o[k + 1] - o[k];
+            if (chunk <= 0) {
+              out[k] = wp_count_doc(T, b, n);
+              continue;
+            }
+            int64_t tot = T.post_add;
+            bool bad = T.n_added && wp_has_added(T, b, n, 0, n);
+            for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
+              const int64_t x = wp_count_range(T, b, n, s0, std::min(n, s0 + chunk));
+              if (x < 0) bad = true;
+              tot += x;
+            }
+            out[k] = (bad || tot > 0x7FFFFFFF) ? kBpeHost : (int32_t)tot;
+          }
+        });
+      for (auto& x : th) x.join();
+    }
+    return to_numpy(std::move(out));
+  }, py::arg("data"), py::arg("off"), py::arg("slots"), py::arg("mask"), py::arg("pool"), py::arg("flags"),
+        py::arg("cls_shift"), py::arg("self_bit"), py::arg("max_chars"), py::arg("longest"), py::arg("added"),
+        py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0);
   m.def("fmt_f64", [](double x) { return fmt_f64(x); });
   m.def("fmt_fixed", [](double x, int prec) { return fmt_fixed(x, prec); });
   m.def("contains_byte", [](py::array_t<uint8_t, py::array::c_style> a, int v) {

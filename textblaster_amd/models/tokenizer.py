@@ -12,7 +12,9 @@ tokenizers library's parallel ``encode_batch``. GPT-2-style byte-level BPE token
 :class:`BpeSpec` (:meth:`TokenCounterModel.bpe_spec`): the merge table as an open-addressed hash
 table plus the byte ids, which the device pipeline counts with (csrc/common/bpe.h, k_bpe_count)
 and ``count_native`` runs on the host (same algorithm; documents it cannot count exactly are
-counted by ``tokenizers``).
+counted by ``tokenizers``). WordPiece tokenizers (BertNormalizer + BertPreTokenizer, the BERT family)
+get a :class:`WordPieceSpec` instead (:meth:`TokenCounterModel.wordpiece_spec`): the vocabulary as an
+open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count).
 """
 from __future__ import annotations
 
@@ -158,6 +160,79 @@ def build_bpe_spec(tj: dict) -> Optional[BpeSpec]:
                    off if added else [], post)
 
 
+@dataclasses.dataclass
+class WordPieceSpec:
+    """Device tables of a WordPiece tokenizer (csrc/common/wordpiece.h DevWp)."""
+    slots: np.ndarray      # uint64 [2 * (mask + 1)]: (key, value) pairs
+    mask: int
+    pool: np.ndarray       # uint8: piece bytes
+    flags: int             # WP_LOWER | WP_CHINESE
+    cls_shift: int         # class bits of wp_classes.inc: 0 clean_text, 2 not
+    self_bit: int          # "normalises to itself" bit non-ASCII code points must carry, 0 = cased
+    max_chars: int         # max_input_chars_per_word
+    longest: int           # bytes of the longest piece
+    added: np.ndarray      # uint8: added-token contents, concatenated
+    added_off: List[int]   # [n_added + 1]
+    post_add: int          # tokens the post-processor adds
+
+
+WP_LOWER, WP_CHINESE = 1, 2  # csrc/common/wordpiece.h kWpLower, kWpChinese
+
+
+def build_wordpiece_spec(tj: dict) -> Optional[WordPieceSpec]:
+    """WordPieceSpec of a parsed tokenizer.json, or None when the tokenizer is not a WordPiece model
+    behind BertNormalizer + BertPreTokenizer that the device counter reproduces exactly (no
+    truncation / padding, the unknown token in the vocabulary, a known post-processor, at most
+    MAX_ADDED added tokens, none of them matched on normalised text)."""
+    from .. import native
+
+    m = tj.get("model") or {}
+    nz, pt = tj.get("normalizer") or {}, tj.get("pre_tokenizer") or {}
+    if m.get("type") != "WordPiece" or nz.get("type") != "BertNormalizer" or pt.get("type") != "BertPreTokenizer":
+        return None
+    if tj.get("truncation") is not None or tj.get("padding") is not None:
+        return None
+    vocab = m.get("vocab") or {}
+    if not isinstance(vocab, dict) or m.get("unk_token") not in vocab:
+        return None
+    post = _post_add(tj.get("post_processor"))
+    if post is None:
+        return None
+    toks = [t for t in tj.get("added_tokens") or [] if t.get("content")]
+    if len(toks) > MAX_ADDED or any(t.get("normalized") for t in toks):
+        return None
+    max_chars = m.get("max_input_chars_per_word", 100)
+    prefix = m.get("continuing_subword_prefix", "##")
+    if not isinstance(max_chars, int) or not 0 <= max_chars < 2 ** 31 or not isinstance(prefix, str):
+        return None
+    lower = bool(nz.get("lowercase", True))
+    strip = lower if nz.get("strip_accents") is None else bool(nz.get("strip_accents"))
+    # pieces: every entry as a word-initial piece, and behind the prefix as a continuation
+    pieces, cont = [], []
+    for s in vocab:
+        if s:
+            pieces.append(s.encode("utf-8"))
+            cont.append(0)
+        if s.startswith(prefix) and len(s) > len(prefix):
+            pieces.append(s[len(prefix):].encode("utf-8"))
+            cont.append(1)
+    if not pieces:
+        return None
+    off = np.zeros(len(pieces) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in pieces], out=off[1:])
+    pool = np.frombuffer(b"".join(pieces), dtype=np.uint8).copy()
+    slots, mask, longest = native.host().wp_build_table(pool, off, np.array(cont, dtype=np.uint8))
+    added = [t["content"].encode("utf-8") for t in toks]
+    aoff = [0]
+    for t in added:
+        aoff.append(aoff[-1] + len(t))
+    return WordPieceSpec(slots, int(mask), pool, (WP_LOWER if lower else 0) | (WP_CHINESE if nz.get(
+        "handle_chinese_chars", True) else 0), 0 if nz.get("clean_text", True) else 2,
+        {(False, False): 0, (True, False): 1 << 4, (False, True): 1 << 5, (True, True): 1 << 6}[(lower, strip)],
+        max_chars, int(longest), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
+        aoff if added else [], post)
+
+
 class TokenCounterModel:
     def __init__(self, path: str):
         from tokenizers import Tokenizer
@@ -165,6 +240,7 @@ class TokenCounterModel:
         self.path = path
         self.tok = Tokenizer.from_file(path)
         self._spec = False
+        self._wp_spec = False
 
     def count(self, texts: List[str]) -> List[int]:
         if not texts:
@@ -179,22 +255,78 @@ class TokenCounterModel:
                 self._spec = build_bpe_spec(json.load(f))
         return self._spec
 
+    def wordpiece_spec(self) -> Optional[WordPieceSpec]:
+        """Device/native tables when this is a BERT-style WordPiece tokenizer (else None); built once."""
+        if self._wp_spec is False:
+            with open(self.path, encoding="utf-8") as f:
+                self._wp_spec = build_wordpiece_spec(json.load(f))
+        return self._wp_spec
+
+    def device_spec(self):
+        """The spec the device path counts with: :class:`BpeSpec`, :class:`WordPieceSpec` or None."""
+        return self.bpe_spec() or self.wordpiece_spec()
+
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
-        """Token counts of packed UTF-8 documents with the native byte-level BPE counter (host
-        emulation of k_bpe_count); documents it returns -2 for (added-token text, invalid UTF-8,
-        pre-tokens over 64 bytes) are counted by ``tokenizers``. Needs :meth:`bpe_spec`."""
+        """Token counts of packed UTF-8 documents with the native counter of whichever spec the
+        tokenizer has (host emulation of k_bpe_count / k_wp_count); documents it returns -2 for
+        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, WordPiece text the
+        normalizer would change beyond ASCII case) are counted by ``tokenizers``."""
         from .. import native
 
-        sp = self.bpe_spec()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, np.int64)
+        sp = self.device_spec()
         if sp is None:
-            raise Unexpected("count_native needs a byte-level BPE tokenizer")
-        out = native.host().bpe_count(np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, np.int64),
-                                      sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
-                                      nthreads).astype(np.int64)
+            raise Unexpected("count_native needs a byte-level BPE or a WordPiece tokenizer")
+        out = count_spec(sp, data, off, nthreads).astype(np.int64)
         bad = np.nonzero(out < 0)[0]
         if len(bad):
             out[bad] = self.count([bytes(data[off[k]:off[k + 1]]).decode("utf-8", "replace") for k in bad.tolist()])
         return out
+
+
+def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: int = 0) -> np.ndarray:
+    """The native counter's raw result (int32 counts, -2 = count on the host) for either kind of
+    spec; ``chunk`` > 0 counts each chunk-byte range on its own, as the kernels' lanes do."""
+    from .. import native
+
+    h = native.host()
+    if isinstance(sp, WordPieceSpec):
+        return h.wp_count(data, off, sp.slots, sp.mask, sp.pool, sp.flags, sp.cls_shift, sp.self_bit, sp.max_chars,
+                          sp.longest, sp.added, sp.added_off, sp.post_add, nthreads, chunk)
+    return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
+                       nthreads, chunk)
+
+
+def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
+                              lowercase: bool = False) -> str:
+    """Train a BERT-format WordPiece tokenizer (BertNormalizer, BertPreTokenizer, ``[CLS] $A [SEP]``
+    template, the five BERT special tokens, ``vocab_size`` entries) on the synthetic Zipf corpus
+    and save it as ``path`` (kept if it already exists): the stand-in for bert-base-cased /
+    -uncased, which cannot be downloaded here."""
+    if os.path.isfile(path):
+        return path
+    from tokenizers import Tokenizer, decoders, models, normalizers, pre_tokenizers, processors, trainers
+
+    from ..utils import synth
+
+    texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
+    tok = Tokenizer(models.WordPiece(unk_token="[UNK]"))
+    tok.normalizer = normalizers.BertNormalizer(clean_text=True, handle_chinese_chars=True, strip_accents=None,
+                                                lowercase=lowercase)
+    tok.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
+    tok.decoder = decoders.WordPiece(prefix="##")
+    special = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"]
+    tr = trainers.WordPieceTrainer(vocab_size=vocab_size, special_tokens=special, show_progress=False)
+    tok.train_from_iterator(texts, tr)
+    tok.post_processor = processors.TemplateProcessing(
+        single="[CLS] $A [SEP]", pair="[CLS] $A [SEP] $B:1 [SEP]:1",
+        special_tokens=[("[CLS]", tok.token_to_id("[CLS]")), ("[SEP]", tok.token_to_id("[SEP]"))])
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    tok.save(tmp)
+    os.replace(tmp, path)
+    return path
 
 
 def train_synthetic_bpe(path: str, vocab_size: int = 50257, n_docs: int = 20000, seed: int = 1) -> str:

@@ -127,6 +127,8 @@ _SIGS = {
     "tb_html_sizes": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P],
     "tb_html_scatter": [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _U32, _P, _P],
     "tb_bpe_count": [_P, _P, _P, _P, _P, _I32, _P],
+    "tb_wp_count": [_P, _P, _P, _P, _P, _I32, _P],
+    "tb_sizeof_wp": [],
     "tb_abi_version": [], "tb_block_threads": [], "tb_phase_slots": [], "tb_stage_waves": [],
     "tb_sizeof_pre_doc": [], "tb_sizeof_gr_export": [], "tb_sizeof_gate": [], "tb_sizeof_resolve": [],
     "tb_sizeof_bpe": [], "tb_sizeof_plan": [], "tb_sizeof_stage": [], "tb_sizeof_c4": [],
@@ -179,6 +181,38 @@ class BpeTables:
         for i, v in enumerate(spec.added_off):
             st.added_off[i] = v
         st.post_add = spec.post_add
+        self.struct = st
+
+
+class DevWp(ctypes.Structure):
+    """csrc/common/wordpiece.h DevWp (checked against tb_sizeof_wp)."""
+    _fields_ = [("slots", _P), ("pool", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
+                ("asc", ctypes.c_uint64 * 4), ("mask", _U32), ("flags", _U32), ("cls_shift", _U32),
+                ("self_bit", _U32), ("max_chars", _I32), ("longest", _I32), ("post_add", _I32), ("n_added", _I32),
+                ("added_off", _I32 * 9)]
+
+
+class WpTables:
+    """A WordPiece tokenizer's tables in HBM (models/tokenizer.py WordPieceSpec) and the kernel's
+    parameter block pointing at them."""
+
+    def __init__(self, spec, cls_tables, ascii_classes):
+        from . import hiprt
+
+        if len(spec.added_off) > 9:
+            raise DeviceError("wordpiece: too many added tokens")
+        if len(spec.slots) != 2 * (spec.mask + 1) or spec.longest < 1:
+            raise DeviceError("wordpiece: vocabulary table shape")
+        self.arrays = [hiprt.to_device(a) for a in (spec.slots, spec.pool, cls_tables[0], cls_tables[1], spec.added)]
+        st = DevWp()
+        st.slots, st.pool, st.cls1, st.cls2, st.added = [a.data_ptr() for a in self.arrays]
+        for i in range(4):
+            st.asc[i] = int(ascii_classes[i])
+        st.mask, st.flags, st.cls_shift, st.self_bit = spec.mask, spec.flags, spec.cls_shift, spec.self_bit
+        st.max_chars, st.longest, st.post_add = spec.max_chars, spec.longest, spec.post_add
+        st.n_added = max(len(spec.added_off) - 1, 0)
+        for i, v in enumerate(spec.added_off):
+            st.added_off[i] = v
         self.struct = st
 
 
@@ -433,6 +467,33 @@ class Kernels:
         rc = self.lib.tb_bpe_count(self.stream(), ctypes.byref(tabs.struct), text.data_ptr(), off.data_ptr(),
                                    _ptr(n_dev), n_max, counts.data_ptr())
         _check(rc, "tb_bpe_count")
+
+    def wp_tables(self, spec) -> WpTables:
+        from .. import native
+
+        if self.lib.tb_sizeof_wp() != ctypes.sizeof(DevWp):
+            raise DeviceError("libtbhip.so DevWp layout differs from the binding; rebuild")
+        h = native.host()
+        return WpTables(spec, h.wp_classes(), h.wp_ascii(spec.cls_shift))
+
+    def wp_count(self, tabs: WpTables, text, off, n_dev, n_max: int, counts):
+        """k_wp_count: WordPiece token counts under bpe_count's contract (csrc/hip/wordpiece.hip)."""
+        if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
+            raise DeviceError("wp_count: operand shapes")
+        rc = self.lib.tb_wp_count(self.stream(), ctypes.byref(tabs.struct), text.data_ptr(), off.data_ptr(),
+                                  _ptr(n_dev), n_max, counts.data_ptr())
+        _check(rc, "tb_wp_count")
+
+    def token_tables(self, spec):
+        """The device tables of a token counter spec of either kind."""
+        from ..models.tokenizer import WordPieceSpec
+
+        return self.wp_tables(spec) if isinstance(spec, WordPieceSpec) else self.bpe_tables(spec)
+
+    def token_count(self, tabs, text, off, n_dev, n_max: int, counts):
+        """k_wp_count or k_bpe_count, by the kind of ``tabs``."""
+        fn = self.wp_count if isinstance(tabs, WpTables) else self.bpe_count
+        fn(tabs, text, off, n_dev, n_max, counts)
 
     def resolve(self, rp, recs, ndocs, flags, versions, fail, status, fver, lanes, sc, out, out_off, rows, err):
         """K16: k_resolve + four scans + k_compact (see tb_resolve). ``recs``: record buffers by

@@ -581,11 +581,12 @@ class DeviceRunner:
                     self.resolve_t = self._to_dev(blob)
                     # int64 fields per document read from each record buffer (launch-time check)
                     self.resolve_need = [w for w, _ in self.stage_layout] + [7] * len(plan.c4_steps)
-            # trailing TokenCounter steps with a byte-level BPE tokenizer: counted on the device
-            # after K16 (token_counters: [(step, BpeSpec)]; device_tokens=0 leaves them to the host)
+            # trailing TokenCounter steps with a byte-level BPE or a WordPiece tokenizer: counted on
+            # the device after K16 (token_counters: [(step, BpeSpec | WordPieceSpec)];
+            # device_tokens=0 leaves them to the host)
             self.bpe = []
             if self.resolve_t is not None and tu.device_tokens:
-                self.bpe = [(i, self.k.bpe_tables(sp)) for i, sp in (token_counters or [])]
+                self.bpe = [(i, self.k.token_tables(sp)) for i, sp in (token_counters or [])]
             # K18: the metadata column formatted on the device after K16 and the token counts
             self.meta_t = None
             if self.resolve_t is not None and tu.device_meta:
@@ -1226,7 +1227,7 @@ class DeviceRunner:
             # entry of the kept-count scan, read by the kernel)
             r_tok = rt.empty(ndocs, np.int32)
             with self._ktimed(b.keep, "bpe_count"):
-                self.k.bpe_count(tabs, r_out, r_off, r_sc[3 * ndocs - 1:3 * ndocs], ndocs, r_tok)
+                self.k.token_count(tabs, r_out, r_off, r_sc[3 * ndocs - 1:3 * ndocs], ndocs, r_tok)
             b.keep.append(r_tok)
             res_d = res_d + ((si, r_tok),)
         if self.meta_t is not None:
@@ -1408,12 +1409,13 @@ class EmulatedRunner:
                                                           [np.ascontiguousarray(o) for _, o in vl])
             resolved = Resolved(fail, st, out, out_off, rows)
             if self.bpe:
-                # k_bpe_count's algorithm (csrc/common/bpe.h) over the kept outputs
+                # k_bpe_count's / k_wp_count's algorithm (csrc/common/bpe.h, wordpiece.h) over the
+                # kept outputs
+                from ..models.tokenizer import count_spec
+
                 nk = int(np.count_nonzero(st == 0))
                 ko = np.ascontiguousarray(out_off[:nk + 1])
-                resolved.tokens = {
-                    si: h.bpe_count(out, ko, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off,
-                                    sp.post_add, self.nthreads) for si, sp in self.bpe}
+                resolved.tokens = {si: count_spec(sp, out, ko, self.nthreads) for si, sp in self.bpe}
             if self.meta_blob is not None:
                 nk, nx = resolved.counts()
                 toks = [np.ascontiguousarray(resolved.tokens[si], dtype=np.int32) for si, _ in self.bpe]

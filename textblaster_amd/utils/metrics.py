@@ -87,9 +87,11 @@ DEVICE_META_FALLBACK_TOTAL = Counter("tb_device_meta_fallback_total",
                                      "fallback.", registry=REGISTRY)
 BPE_HOST_DOCS_TOTAL = Counter("tb_bpe_host_docs_total",
                               "Kept documents whose TokenCounter count the device handed to the host tokenizer "
-                              "(added-token text or a pre-token over 64 bytes).", registry=REGISTRY)
+                              "(added-token text, a BPE pre-token over 2048 bytes, WordPiece text its normalizer "
+                              "changes beyond ASCII case, or a tokenizer with no device counter).", registry=REGISTRY)
 BPE_DEVICE_DOCS_TOTAL = Counter("tb_bpe_device_docs_total",
-                                "Kept documents whose TokenCounter count came from k_bpe_count.", registry=REGISTRY)
+                                "Kept documents whose TokenCounter count came from k_bpe_count / k_wp_count.",
+                                registry=REGISTRY)
 RANK = Gauge("tb_rank", "Data-parallel rank of this process.", registry=REGISTRY)
 WORLD_SIZE = Gauge("tb_world_size", "Number of data-parallel ranks.", registry=REGISTRY)
 GLOBAL_DOCS = Gauge("tb_global_docs_total", "All-reduced document counters (rank 0).", ["kind"],
