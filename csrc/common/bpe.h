@@ -27,6 +27,10 @@
 // pre-token, up to kBpeMaxLong bytes). A document goes back to the host tokenizer (count -2) when
 // it contains the text of an added token (HF splits on those before pre-tokenizing), holds invalid
 // UTF-8, or has a pre-token longer than kBpeMaxLong bytes.
+//
+// The counting loops (bpe_count_span / _range / _doc) take the pre-tokenizer as a policy: BpeGpt2
+// below is the regex above; BpeSplit (bpe_split.h) is the Split(regex) + ByteLevel(use_regex=false)
+// layout of Llama-3, cl100k_base and Qwen2, with ignore_merges and added tokens kept in memory.
 #pragma once
 #include "tb_common.h"
 
@@ -42,6 +46,11 @@ constexpr int32_t kBpeHost = -2;  // count it on the host
 constexpr int32_t kBpeLong = -3;
 constexpr int kBpeMaxLong = 2048;  // longest pre-token merged on the device
 
+// the pre-tokenizer: GPT-2's ByteLevel regex, or Split(pattern A / B) + ByteLevel(use_regex=false)
+enum BpeKind : int { kBpeGpt2 = 0, kBpeSplitA = 1, kBpeSplitB = 2 };
+constexpr int kBpeSplitMaxAdded = 1024;
+constexpr int kBpeSplitMaxAddedBytes = 65536;
+
 enum BpeCls : int { BPE_O = 0, BPE_L = 1, BPE_N = 2, BPE_W = 3 };
 
 struct DevBpe {
@@ -55,6 +64,16 @@ struct DevBpe {
   int32_t n_added;
   int32_t added_off[kBpeMaxAdded + 1];
   int32_t post_add;          // tokens the post-processor adds to every encoding
+  // split-regex family only (kind != kBpeGpt2, csrc/common/bpe_split.h): up to kBpeSplitMaxAdded
+  // added tokens with their offsets in memory, and the vocabulary for ignore_merges
+  const int32_t* aoff;       // [n_added + 1]: offsets into added
+  const uint64_t* vslots;    // [2 * (vmask + 1)]: WpSlot pairs (wordpiece.h) over the entries' raw bytes
+  const uint8_t* vpool;      // the entries' raw bytes
+  uint64_t amask[4];         // bit x: an added token starts with byte x
+  uint32_t vmask;
+  int32_t vlongest;          // bytes of the longest vocabulary entry
+  int32_t kind;              // kBpeGpt2 / kBpeSplitA / kBpeSplitB
+  int32_t ignore_merges;     // a pre-token that is a vocabulary entry is one token
 };
 
 TB_HD uint64_t bpe_hash(uint64_t k) {
@@ -324,40 +343,73 @@ TB_HD int64_t bpe_first_start(const DevBpe& T, const uint8_t* b, int64_t n, int6
   return i;
 }
 
-// Tokens (after merges) of the pre-tokens that start in [first_start(s0), first_start(s1)); a
-// pre-token [s, e) over kBpeMaxWord bytes is handed to on_long(s, e) (its tokens, or < 0: fail).
+// The pre-tokenizer as a policy of the counting loops below: where a range's first token starts
+// (first_start) and where its last one ends (range_end: the range's own end when token starts are
+// local, else the next range's first start), the sequential rule (next_token), the whole-piece
+// vocabulary lookup of ignore_merges (whole) and the added-token scan (has_added).
+struct BpeGpt2 {
+  static constexpr bool kSyncSplit = false;
+  static TB_HD int64_t first_start(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0) {
+    return bpe_first_start(T, b, n, s0);
+  }
+  static TB_HD int64_t range_end(const DevBpe&, const uint8_t*, int64_t, int64_t s1) { return s1; }
+  static TB_HD int64_t next_token(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s) {
+    return bpe_next_token(T, b, n, s);
+  }
+  static TB_HD bool whole(const DevBpe&, const uint8_t*, int64_t) { return false; }
+  static TB_HD bool has_added(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1) {
+    return bpe_has_added(T, b, n, s0, s1);
+  }
+};
+
+// Tokens (after merges) of the pre-tokens that start in [s, stop), s and stop token starts (or n);
+// a pre-token [s, e) over kBpeMaxWord bytes is handed to on_long(s, e) (its tokens, or < 0: fail).
 // -1: count the document on the host (invalid UTF-8, or on_long failed).
 struct BpeNoLong {
   TB_HD int64_t operator()(int64_t, int64_t) const { return -1; }
 };
-// (kMerge = false: short pre-tokens are only delimited, not merged; they count 0)
-template <bool kMerge = true, class LongF = BpeNoLong>
-TB_HD int64_t bpe_count_range(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1, BpeArr c,
-                              BpeArr r, LongF&& on_long = LongF{}) {
-  int64_t s = s0 <= 0 ? 0 : bpe_first_start(T, b, n, s0);
-  if (s < 0) return -1;
+// (kMerge = false: short pre-tokens are only delimited, not merged; they count 0, as do whole-piece
+// hits of any length, which the kMerge = true pass has counted)
+template <bool kMerge = true, class P = BpeGpt2, class LongF = BpeNoLong>
+TB_HD int64_t bpe_count_span(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s, int64_t stop, BpeArr c,
+                             BpeArr r, LongF&& on_long = LongF{}) {
   int64_t total = 0;
-  while (s < n && s < s1) {
-    const int64_t e = bpe_next_token(T, b, n, s);
+  while (s < n && s < stop) {
+    const int64_t e = P::next_token(T, b, n, s);
     if (e <= s) return -1;
     if (e - s > kBpeMaxWord) {
-      const int64_t k = on_long(s, e);
-      if (k < 0) return -1;
-      total += k;
+      if (P::whole(T, b + s, e - s)) {
+        total += kMerge ? 1 : 0;
+      } else {
+        const int64_t k = on_long(s, e);
+        if (k < 0) return -1;
+        total += k;
+      }
     } else if (kMerge) {
-      total += bpe_word(T, b + s, (int)(e - s), c, r);
+      total += P::whole(T, b + s, e - s) ? 1 : bpe_word(T, b + s, (int)(e - s), c, r);
     }
     s = e;
   }
   return total;
 }
 
+// bpe_count_span over the pre-tokens that start in [first_start(s0), range_end(s1))
+template <bool kMerge = true, class P = BpeGpt2, class LongF = BpeNoLong>
+TB_HD int64_t bpe_count_range(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1, BpeArr c,
+                              BpeArr r, LongF&& on_long = LongF{}) {
+  const int64_t s = s0 <= 0 ? 0 : P::first_start(T, b, n, s0);
+  if (s < 0) return -1;
+  const int64_t stop = P::range_end(T, b, n, s1);
+  if (stop < 0) return -1;
+  return bpe_count_span<kMerge, P>(T, b, n, s, stop, c, r, on_long);
+}
+
 // Token count of one document (kBpeHost: count it on the host), sequentially.
-template <class LongF = BpeNoLong>
+template <class P = BpeGpt2, class LongF = BpeNoLong>
 TB_HD int32_t bpe_count_doc(const DevBpe& T, const uint8_t* b, int64_t n, BpeArr c, BpeArr r,
                             LongF&& on_long = LongF{}) {
-  if (T.n_added && bpe_has_added(T, b, n)) return kBpeHost;
-  const int64_t k = bpe_count_range<true>(T, b, n, 0, n, c, r, on_long);
+  if (T.n_added && P::has_added(T, b, n, 0, n)) return kBpeHost;
+  const int64_t k = bpe_count_span<true, P>(T, b, n, 0, n, c, r, on_long);
   if (k < 0 || k + T.post_add > 0x7FFFFFFF) return kBpeHost;
   return (int32_t)(k + T.post_add);
 }

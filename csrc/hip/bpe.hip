@@ -11,9 +11,14 @@
 // A pre-token over those 64-byte arrays marks the document kBpeLong; k_bpe_long then recounts it
 // with one wave per long pre-token (merge arrays of kBpeMaxLong entries, the minimum search spread
 // over the wave).
+//
+// Both kernels are written once over the pre-tokenizer policy (csrc/common/bpe.h): k_bpe_count /
+// k_bpe_long are the GPT-2 instantiation, k_bpe_split_count / k_bpe_split_long the split-regex
+// one (csrc/common/bpe_split.h: Llama-3, cl100k_base, Qwen2), whose lanes start at their range's
+// first sync point and stop at the next lane's.
 #include <hip/hip_runtime.h>
 
-#include "../common/bpe.h"
+#include "../common/bpe_split.h"
 
 using namespace tb;
 
@@ -23,10 +28,43 @@ constexpr int kBpeLanes = 64;
 constexpr int kBpeMinChunk = 16;  // bytes per lane at least (short documents use fewer lanes)
 constexpr int kBpeGrid = 8192;
 
-__global__ __launch_bounds__(kBpeLanes) void k_bpe_count(DevBpe T, const uint8_t* __restrict__ text,
-                                                         const int64_t* __restrict__ off,
-                                                         const int64_t* __restrict__ n_dev, int32_t n_max,
-                                                         int32_t* __restrict__ counts) {
+// next lane's value (the last lane: its own)
+__device__ __forceinline__ int64_t lane_next_i64(int64_t x) {
+  const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)x, 1, kBpeLanes);
+  const uint32_t hi = (uint32_t)__shfl_down((int)(uint32_t)((uint64_t)x >> 32), 1, kBpeLanes);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// A lane's tokens start in [lo, hi): BpeGpt2 finds lo locally and stops at its byte range's end;
+// BpeSplit (csrc/common/bpe_split.h) has lo = sync(s0) and hi = the next lane's lo, passed down
+// the wave instead of searched twice (lanes past the document hold len). -1 in *lo: invalid UTF-8.
+template <class P>
+__device__ __forceinline__ void lane_span(const DevBpe& T, const uint8_t* b, int64_t len, int64_t s0, int64_t s1,
+                                          int t, int64_t* lo, int64_t* hi) {
+  if (!P::kSyncSplit) {
+    *lo = s0;  // (bpe_count_range resolves both ends)
+    *hi = s1;
+    return;
+  }
+  int64_t a = len;
+  if (s0 < len) a = t == 0 ? 0 : P::first_start(T, b, len, s0);
+  const int64_t nx = lane_next_i64(a < 0 ? len : a);
+  *lo = a;
+  *hi = t == kBpeLanes - 1 ? len : nx;
+}
+
+template <bool kMerge, class P, class LongF>
+__device__ __forceinline__ int64_t lane_count(const DevBpe& T, const uint8_t* b, int64_t len, int64_t lo, int64_t hi,
+                                              BpeArr c, BpeArr r, LongF&& on_long) {
+  if (!P::kSyncSplit) return bpe_count_range<kMerge, P>(T, b, len, lo, hi, c, r, on_long);
+  if (lo < 0) return -1;
+  return bpe_count_span<kMerge, P>(T, b, len, lo, hi, c, r, on_long);
+}
+
+template <class P>
+__device__ __forceinline__ void bpe_count_body(const DevBpe& T, const uint8_t* __restrict__ text,
+                                               const int64_t* __restrict__ off, const int64_t* __restrict__ n_dev,
+                                               int32_t n_max, int32_t* __restrict__ counts) {
   __shared__ uint32_t cs[kBpeMaxWord * kBpeLanes];
   __shared__ uint32_t rs[kBpeMaxWord * kBpeLanes];
   const int t = threadIdx.x;
@@ -38,18 +76,20 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_count(DevBpe T, const uint8_t
     const uint8_t* b = text + s;
     const int64_t chunk = max((int64_t)kBpeMinChunk, (len + kBpeLanes - 1) / kBpeLanes);
     const int64_t s0 = (int64_t)t * chunk;
+    const int64_t s1 = min(len, s0 + chunk);
     long long cnt = 0;
     int bad = 0, lng = 0;
+    int64_t lo, hi;
+    lane_span<P>(T, b, len, s0, s1, t, &lo, &hi);
     if (s0 < len) {
-      const int64_t s1 = min(len, s0 + chunk);
-      if (T.n_added && bpe_has_added(T, b, len, s0, s1)) {
+      if (T.n_added && P::has_added(T, b, len, s0, s1)) {
         bad = 1;
       } else {
-        const int64_t x = bpe_count_range<true>(T, b, len, s0, s1, BpeArr{cs + t, kBpeLanes},
-                                                BpeArr{rs + t, kBpeLanes}, [&](int64_t, int64_t) -> int64_t {
-                                                  lng = 1;
-                                                  return 0;
-                                                });
+        const int64_t x = lane_count<true, P>(T, b, len, lo, hi, BpeArr{cs + t, kBpeLanes}, BpeArr{rs + t, kBpeLanes},
+                                              [&](int64_t, int64_t) -> int64_t {
+                                                lng = 1;
+                                                return 0;
+                                              });
         if (x < 0) bad = 1;
         else cnt = x;
       }
@@ -62,6 +102,21 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_count(DevBpe T, const uint8_t
       counts[k] = (any_bad || tot > 0x7FFFFFFF) ? kBpeHost : any_long ? (int32_t)(kBpeLong - tot) : (int32_t)tot;
     }
   }
+}
+
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_count(DevBpe T, const uint8_t* __restrict__ text,
+                                                         const int64_t* __restrict__ off,
+                                                         const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                         int32_t* __restrict__ counts) {
+  bpe_count_body<BpeGpt2>(T, text, off, n_dev, n_max, counts);
+}
+
+// k_bpe_count for the split-regex family (patterns A and B, T.kind)
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_split_count(DevBpe T, const uint8_t* __restrict__ text,
+                                                               const int64_t* __restrict__ off,
+                                                               const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                               int32_t* __restrict__ counts) {
+  bpe_count_body<BpeSplit>(T, text, off, n_dev, n_max, counts);
 }
 
 constexpr int kBpeLongList = 32;  // long pre-tokens of one document counted on the device
@@ -117,10 +172,10 @@ __device__ int bpe_word_long_wave(const DevBpe& T, const uint8_t* w, int L, uint
 // Documents k_bpe_count marked (count <= kBpeLong): the lanes delimit their ranges' pre-tokens
 // again without merging the short ones (their tokens are in the mark), collect the long ones (up
 // to kBpeLongList per document) and the wave merges them one after another.
-__global__ __launch_bounds__(kBpeLanes) void k_bpe_long(DevBpe T, const uint8_t* __restrict__ text,
-                                                        const int64_t* __restrict__ off,
-                                                        const int64_t* __restrict__ n_dev, int32_t n_max,
-                                                        int32_t* __restrict__ counts) {
+template <class P>
+__device__ __forceinline__ void bpe_long_body(const DevBpe& T, const uint8_t* __restrict__ text,
+                                              const int64_t* __restrict__ off, const int64_t* __restrict__ n_dev,
+                                              int32_t n_max, int32_t* __restrict__ counts) {
   __shared__ uint32_t lc[kBpeMaxLong];
   __shared__ uint64_t lv[kBpeMaxLong];
   __shared__ int16_t lnx[kBpeMaxLong];
@@ -142,9 +197,11 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_long(DevBpe T, const uint8_t*
     __syncthreads();
     long long cnt = 0;
     int bad = 0;
+    int64_t lo, hi;
+    lane_span<P>(T, b, len, s0, min(len, s0 + chunk), t, &lo, &hi);
     if (s0 < len) {
-      const int64_t x = bpe_count_range<false>(T, b, len, s0, min(len, s0 + chunk), BpeArr{nullptr, 0},
-                                               BpeArr{nullptr, 0}, [&](int64_t a, int64_t e) -> int64_t {
+      const int64_t x = lane_count<false, P>(T, b, len, lo, hi, BpeArr{nullptr, 0}, BpeArr{nullptr, 0},
+                                             [&](int64_t a, int64_t e) -> int64_t {
                                           if (e - a > kBpeMaxLong) return -1;
                                           const uint32_t q = atomicAdd(&nlong, 1u);
                                           if (q >= (uint32_t)kBpeLongList) return -1;
@@ -165,18 +222,45 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_long(DevBpe T, const uint8_t*
   }
 }
 
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_long(DevBpe T, const uint8_t* __restrict__ text,
+                                                        const int64_t* __restrict__ off,
+                                                        const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                        int32_t* __restrict__ counts) {
+  bpe_long_body<BpeGpt2>(T, text, off, n_dev, n_max, counts);
+}
+
+// k_bpe_long for the split-regex family (a long pre-token that is a vocabulary entry under
+// ignore_merges was counted by k_bpe_split_count and is not listed here)
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_split_long(DevBpe T, const uint8_t* __restrict__ text,
+                                                              const int64_t* __restrict__ off,
+                                                              const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                              int32_t* __restrict__ counts) {
+  bpe_long_body<BpeSplit>(T, text, off, n_dev, n_max, counts);
+}
+
 }  // namespace
 
 // counts[k] for documents k < min(*n_dev, n_max) (n_dev may be null): text + off[k] .. off[k + 1]
 extern "C" int tb_bpe_count(hipStream_t stream, const DevBpe* T, const uint8_t* text, const int64_t* off,
                             const int64_t* n_dev, int32_t n_max, int32_t* counts) {
   if (n_max <= 0) return 0;
-  if (T == nullptr || T->n_added < 0 || T->n_added > kBpeMaxAdded) return (int)hipErrorInvalidValue;
+  if (T == nullptr || T->n_added < 0) return (int)hipErrorInvalidValue;
+  const bool split = T->kind == kBpeSplitA || T->kind == kBpeSplitB;
+  if (split ? (T->n_added > kBpeSplitMaxAdded || (T->n_added && (T->aoff == nullptr || T->added == nullptr)) ||
+               (T->ignore_merges && (T->vslots == nullptr || T->vpool == nullptr || T->vlongest < 1)))
+            : (T->kind != kBpeGpt2 || T->n_added > kBpeMaxAdded))
+    return (int)hipErrorInvalidValue;
   const int grid = n_max < kBpeGrid ? n_max : kBpeGrid;
-  hipLaunchKernelGGL(k_bpe_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
   // the documents with pre-tokens over kBpeMaxWord bytes (grid-stride; the others are skipped)
   const int grid_long = n_max < kBpeGrid / 4 ? n_max : kBpeGrid / 4;
-  hipLaunchKernelGGL(k_bpe_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+  if (split) {
+    hipLaunchKernelGGL(k_bpe_split_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+    hipLaunchKernelGGL(k_bpe_split_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
+                       counts);
+  } else {
+    hipLaunchKernelGGL(k_bpe_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+    hipLaunchKernelGGL(k_bpe_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+  }
   return (int)hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cstring>
 #include <optional>
 #include <thread>
@@ -11,6 +12,7 @@
 
 #include "../common/badwords.h"
 #include "../common/bpe.h"
+#include "../common/bpe_split.h"
 #include "../common/bpe_classes.inc"
 #include "../common/wordpiece.h"
 #include "../common/wp_classes.inc"
@@ -361,13 +363,25 @@ PYBIND11_MODULE(_tbhost, m) {
                         py::array_t<uint32_t, py::array::c_style> byte_id, py::array_t<uint64_t, py::array::c_style> keys,
                         py::array_t<uint64_t, py::array::c_style> vals, uint32_t mask,
                         py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
-                        int nthreads, int64_t chunk) {
-    // host emulation of k_bpe_count: per document the token count, or kBpeHost. chunk > 0: the
-    // wave split — the pre-tokens starting in each chunk-byte range counted independently
-    // (bpe_count_range), as the kernel's lanes do
+                        int nthreads, int64_t chunk, int kind, bool ignore_merges,
+                        py::array_t<uint64_t, py::array::c_style> vslots, uint32_t vmask,
+                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest) {
+    // host emulation of k_bpe_count / k_bpe_split_count (kind: BpeKind): per document the token
+    // count, or kBpeHost. chunk > 0: the wave split — the pre-tokens starting in each chunk-byte
+    // range counted independently (bpe_count_range), as the kernel's lanes do
+    const bool split = kind == kBpeSplitA || kind == kBpeSplitB;
     if (byte_id.size() != 256 || (size_t)keys.size() != (size_t)mask + 1 || vals.size() != keys.size() ||
-        added_off.size() > kBpeMaxAdded + 1 || (added_off.size() && added_off.back() > added.size()))
+        (!split && kind != kBpeGpt2) || added_off.size() > (size_t)(split ? kBpeSplitMaxAdded : kBpeMaxAdded) + 1 ||
+        (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size())) ||
+        !std::is_sorted(added_off.begin(), added_off.end()) || (ignore_merges && !split) ||
+        (ignore_merges && ((size_t)vslots.size() != 2 * ((size_t)vmask + 1) || vlongest < 1)))
       throw std::invalid_argument("bpe_count: operand shapes");
+    if (ignore_merges)  // every listed entry lies in the pool
+      for (size_t i = 0; i <= vmask; ++i) {
+        const uint64_t v = vslots.data()[2 * i + 1];
+        if (v != kWpEmpty && (v >> 32) + (uint32_t)v > (uint64_t)vpool.size())
+          throw std::invalid_argument("bpe_count: vocabulary table");
+      }
     const int64_t nd = off.size() - 1;
     std::vector<int32_t> out(nd > 0 ? nd : 0);
     DevBpe T{};
@@ -379,11 +393,23 @@ PYBIND11_MODULE(_tbhost, m) {
     T.added = added.data();
     T.mask = mask;
     T.n_added = added_off.empty() ? 0 : (int32_t)added_off.size() - 1;
-    for (size_t i = 0; i < added_off.size(); ++i) T.added_off[i] = added_off[i];
+    if (split) {
+      T.aoff = added_off.data();
+      bpe_added_mask(T.added, T.aoff, T.n_added, T.amask);
+      T.vslots = vslots.data();
+      T.vpool = vpool.data();
+      T.vmask = vmask;
+      T.vlongest = vlongest;
+      T.ignore_merges = ignore_merges;
+    } else {
+      for (size_t i = 0; i < added_off.size(); ++i) T.added_off[i] = added_off[i];
+    }
+    T.kind = kind;
     T.post_add = post_add;
     const uint8_t* d = data.data();
     const int64_t* o = off.data();
-    {
+    auto run = [&](auto policy) {
+      using P = decltype(policy);
       py::gil_scoped_release nogil;
       const int nt = std::max(1, std::min<int>(nthreads, (int)(nd / 256) + 1));
       std::vector<std::thread> th;
@@ -404,14 +430,14 @@ PYBIND11_MODULE(_tbhost, m) {
             b = d + o[k];
             const int64_t n = o[k + 1] - o[k];
             if (chunk <= 0) {
-              out[k] = bpe_count_doc(T, b, n, BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
+              out[k] = bpe_count_doc<P>(T, b, n, BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
               continue;
             }
             int64_t tot = T.post_add;
-            bool bad = T.n_added && bpe_has_added(T, b, n);
+            bool bad = T.n_added && P::has_added(T, b, n, 0, n);
             for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
-              const int64_t x = bpe_count_range<true>(T, b, n, s0, std::min(n, s0 + chunk), BpeArr{cbuf, 1},
-                                                      BpeArr{rbuf, 1}, on_long);
+              const int64_t x = bpe_count_range<true, P>(T, b, n, s0, std::min(n, s0 + chunk), BpeArr{cbuf, 1},
+                                                         BpeArr{rbuf, 1}, on_long);
               if (x < 0) bad = true;
               tot += x;
             }
@@ -419,10 +445,43 @@ PYBIND11_MODULE(_tbhost, m) {
           }
         });
       for (auto& x : th) x.join();
-    }
+    };
+    if (split) run(BpeSplit{});
+    else run(BpeGpt2{});
     return to_numpy(std::move(out));
   }, py::arg("data"), py::arg("off"), py::arg("byte_id"), py::arg("keys"), py::arg("vals"), py::arg("mask"),
-        py::arg("added"), py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0);
+        py::arg("added"), py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0,
+        py::arg("kind") = 0, py::arg("ignore_merges") = false,
+        py::arg("vslots") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("vmask") = 0,
+        py::arg("vpool") = py::array_t<uint8_t, py::array::c_style>(0), py::arg("vlongest") = 0);
+  m.def("bpe_split_ends", [](py::bytes text, int kind) -> py::object {
+    // the pre-tokens of pattern A / B (bpe_split_next_token): their end offsets in bytes, None on
+    // invalid UTF-8 (for tests and tools that compare the rules with the library's Split)
+    if (kind != kBpeSplitA && kind != kBpeSplitB) throw std::invalid_argument("bpe_split_ends: kind");
+    const std::string s = text;
+    DevBpe T{};
+    T.cls1 = TB_BPE_CLS_STAGE1;
+    T.cls2 = TB_BPE_CLS_STAGE2;
+    T.kind = kind;
+    std::vector<int64_t> ends;
+    const int64_t n = (int64_t)s.size();
+    for (int64_t p = 0; p < n;) {
+      const int64_t e = bpe_split_next_token(T, reinterpret_cast<const uint8_t*>(s.data()), n, p);
+      if (e <= p) return py::none();
+      ends.push_back(e);
+      p = e;
+    }
+    return to_numpy(std::move(ends));
+  });
+  m.def("bpe_added_mask", [](py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off) {
+    // DevBpe::amask: the 256-bit mask of the added tokens' first bytes
+    if (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size() ||
+                             !std::is_sorted(added_off.begin(), added_off.end())))
+      throw std::invalid_argument("bpe_added_mask: operand shapes");
+    std::vector<uint64_t> m4(4);
+    bpe_added_mask(added.data(), added_off.data(), added_off.empty() ? 0 : (int)added_off.size() - 1, m4.data());
+    return to_numpy(std::move(m4));
+  });
   // ---- WordPiece token counting (csrc/common/wordpiece.h; device kernel csrc/hip/wordpiece.hip) ----
   m.def("wp_classes", []() {
     std::vector<uint16_t> c1(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE1 + sizeof(TB_WP_CLS_STAGE1) / 2);

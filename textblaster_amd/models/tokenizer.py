@@ -12,8 +12,11 @@ tokenizers library's parallel ``encode_batch``. GPT-2-style byte-level BPE token
 :class:`BpeSpec` (:meth:`TokenCounterModel.bpe_spec`): the merge table as an open-addressed hash
 table plus the byte ids, which the device pipeline counts with (csrc/common/bpe.h, k_bpe_count)
 and ``count_native`` runs on the host (same algorithm; documents it cannot count exactly are
-counted by ``tokenizers``). WordPiece tokenizers (BertNormalizer + BertPreTokenizer, the BERT family)
-get a :class:`WordPieceSpec` instead (:meth:`TokenCounterModel.wordpiece_spec`): the vocabulary as an
+counted by ``tokenizers``). So do the byte-level BPE tokenizers serialised as
+Split(regex) + ByteLevel(use_regex=false) with the Llama-3 / cl100k_base pattern or Qwen2's
+(csrc/common/bpe_split.h, k_bpe_split_count): their spec also carries the vocabulary's raw bytes
+for ``ignore_merges`` and up to 1024 added tokens. WordPiece tokenizers (BertNormalizer +
+BertPreTokenizer, the BERT family) get a :class:`WordPieceSpec` instead (:meth:`TokenCounterModel.wordpiece_spec`): the vocabulary as an
 open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count).
 """
 from __future__ import annotations
@@ -75,6 +78,41 @@ class BpeSpec:
     added: np.ndarray      # uint8: added-token contents, concatenated
     added_off: List[int]   # [n_added + 1]
     post_add: int          # tokens the post-processor adds
+    # the split-regex family (csrc/common/bpe_split.h); GPT-2 keeps the defaults
+    kind: int = 0                          # BPE_GPT2 / BPE_SPLIT_A / BPE_SPLIT_B
+    ignore_merges: bool = False
+    vslots: Optional[np.ndarray] = None    # uint64 [2 * (vmask + 1)]: the vocabulary's raw bytes, WpSlot pairs
+    vmask: int = 0
+    vpool: Optional[np.ndarray] = None     # uint8: the entries' raw bytes
+    vlongest: int = 0                      # bytes of the longest entry
+    added_mask: Optional[np.ndarray] = None  # uint64 [4]: first bytes of the added tokens
+
+
+BPE_GPT2, BPE_SPLIT_A, BPE_SPLIT_B = 0, 1, 2  # csrc/common/bpe.h BpeKind
+SPLIT_MAX_ADDED, SPLIT_MAX_ADDED_BYTES = 1024, 65536  # kBpeSplitMaxAdded, kBpeSplitMaxAddedBytes
+# the Split patterns counted on the device: Llama-3 / cl100k_base, and the Qwen2 family
+SPLIT_PATTERN_A = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
+                   r"|\s*[\r\n]+|\s+(?!\S)|\s+")
+SPLIT_PATTERN_B = SPLIT_PATTERN_A.replace(r"\p{N}{1,3}", r"\p{N}")
+
+
+def _split_kind(pt) -> Optional[int]:
+    """BPE_SPLIT_A / _B when the pre-tokenizer is exactly Sequence[Split(Regex(A or B), Isolated),
+    ByteLevel(add_prefix_space=false, use_regex=false)], else None."""
+    if not isinstance(pt, dict) or pt.get("type") != "Sequence":
+        return None
+    pts = pt.get("pretokenizers") or []
+    if len(pts) != 2 or any(not isinstance(q, dict) for q in pts):
+        return None
+    sp, bl = pts
+    if sp.get("type") != "Split" or sp.get("behavior") != "Isolated" or sp.get("invert") is not False:
+        return None
+    if bl.get("type") != "ByteLevel" or bl.get("add_prefix_space") is not False or bl.get("use_regex") is not False:
+        return None
+    pat = sp.get("pattern")
+    if not isinstance(pat, dict) or set(pat) != {"Regex"}:
+        return None
+    return {SPLIT_PATTERN_A: BPE_SPLIT_A, SPLIT_PATTERN_B: BPE_SPLIT_B}.get(pat["Regex"])
 
 
 def _post_add(pp) -> Optional[int]:
@@ -110,20 +148,30 @@ def _post_add(pp) -> Optional[int]:
 
 def build_bpe_spec(tj: dict) -> Optional[BpeSpec]:
     """BpeSpec of a parsed tokenizer.json, or None when the tokenizer is not a byte-level BPE the
-    device counter reproduces exactly (no normalizer, ByteLevel regex pre-tokenizer without prefix
-    space, plain BPE merges, no truncation / padding, known post-processor)."""
+    device counter reproduces exactly: no normalizer, plain BPE merges, no truncation / padding, a
+    known post-processor, and as pre-tokenizer either GPT-2's ByteLevel regex without prefix space
+    (at most MAX_ADDED added tokens, no ignore_merges) or Split(pattern A / B) + ByteLevel without
+    regex (Llama-3, cl100k_base, Qwen2: ignore_merges allowed, no byte_fallback, at most
+    SPLIT_MAX_ADDED added tokens of SPLIT_MAX_ADDED_BYTES bytes together)."""
     from .. import native
 
     m = tj.get("model") or {}
     if m.get("type") != "BPE" or m.get("dropout") not in (None, 0, 0.0) or m.get("continuing_subword_prefix") \
-            or m.get("end_of_word_suffix") or m.get("ignore_merges"):
+            or m.get("end_of_word_suffix"):
         return None
     if tj.get("normalizer") is not None or tj.get("truncation") is not None or tj.get("padding") is not None:
         return None
     pt = tj.get("pre_tokenizer")
-    if pt is not None and pt.get("type") == "Sequence" and len(pt.get("pretokenizers", [])) == 1:
-        pt = pt["pretokenizers"][0]
-    if pt is None or pt.get("type") != "ByteLevel" or pt.get("add_prefix_space") or not pt.get("use_regex", True):
+    kind = _split_kind(pt)
+    if kind is None:
+        kind = BPE_GPT2
+        if m.get("ignore_merges"):
+            return None
+        if pt is not None and pt.get("type") == "Sequence" and len(pt.get("pretokenizers", [])) == 1:
+            pt = pt["pretokenizers"][0]
+        if pt is None or pt.get("type") != "ByteLevel" or pt.get("add_prefix_space") or not pt.get("use_regex", True):
+            return None
+    elif m.get("byte_fallback"):
         return None
     post = _post_add(tj.get("post_processor"))
     if post is None:
@@ -151,13 +199,32 @@ def build_bpe_spec(tj: dict) -> Optional[BpeSpec]:
     u32 = lambda v: np.array(v, dtype=np.uint32)  # noqa: E731
     keys, vals, mask = native.host().bpe_build_table(u32(a), u32(b), u32(rank), u32(nid))
     added = [t["content"].encode("utf-8") for t in tj.get("added_tokens") or [] if t.get("content")]
-    if len(added) > MAX_ADDED:
+    if len(added) > (MAX_ADDED if kind == BPE_GPT2 else SPLIT_MAX_ADDED):
         return None
     off = [0]
     for t in added:
         off.append(off[-1] + len(t))
-    return BpeSpec(byte_id, keys, vals, int(mask), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
+    spec = BpeSpec(byte_id, keys, vals, int(mask), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
                    off if added else [], post)
+    if kind == BPE_GPT2:
+        return spec
+    if off[-1] > SPLIT_MAX_ADDED_BYTES:
+        return None
+    spec.kind = kind
+    spec.ignore_merges = bool(m.get("ignore_merges"))
+    spec.added_mask = native.host().bpe_added_mask(spec.added, spec.added_off)
+    if spec.ignore_merges:
+        # the vocabulary as raw bytes (entries with a character outside the byte-level alphabet
+        # can never equal a pre-token)
+        u2b = {ch: i for i, ch in enumerate(b2u)}
+        entries = [bytes(u2b[ch] for ch in w) for w in vocab if w and all(ch in u2b for ch in w)]
+        voff = np.zeros(len(entries) + 1, dtype=np.int64)
+        np.cumsum([len(e) for e in entries], out=voff[1:])
+        spec.vpool = np.frombuffer(b"".join(entries), dtype=np.uint8).copy()
+        spec.vslots, vmask, longest = native.host().wp_build_table(spec.vpool, voff,
+                                                                   np.zeros(len(entries), dtype=np.uint8))
+        spec.vmask, spec.vlongest = int(vmask), int(longest)
+    return spec
 
 
 @dataclasses.dataclass
@@ -294,8 +361,13 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
     if isinstance(sp, WordPieceSpec):
         return h.wp_count(data, off, sp.slots, sp.mask, sp.pool, sp.flags, sp.cls_shift, sp.self_bit, sp.max_chars,
                           sp.longest, sp.added, sp.added_off, sp.post_add, nthreads, chunk)
+    if sp.kind == BPE_GPT2:
+        return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
+                           nthreads, chunk)
+    none64, none8 = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint8)
     return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
-                       nthreads, chunk)
+                       nthreads, chunk, sp.kind, sp.ignore_merges, none64 if sp.vslots is None else sp.vslots,
+                       sp.vmask, none8 if sp.vpool is None else sp.vpool, sp.vlongest)
 
 
 def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
@@ -349,6 +421,47 @@ def train_synthetic_bpe(path: str, vocab_size: int = 50257, n_docs: int = 20000,
     tr = trainers.BpeTrainer(vocab_size=vocab_size, special_tokens=["<|endoftext|>"], show_progress=False,
                              initial_alphabet=pre_tokenizers.ByteLevel.alphabet())
     tok.train_from_iterator(texts, tr)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    tok.save(tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def train_synthetic_split_bpe(path: str, vocab_size: int = 32000, pattern: str = "A", ignore_merges: bool = True,
+                              n_added: int = 256, n_docs: int = 20000, seed: int = 1) -> str:
+    """Train a Llama-3-format byte-level BPE tokenizer on the synthetic Zipf corpus and save it as
+    ``path`` (kept if it already exists): pre-tokenizer Sequence[Split(pattern A or B, Isolated),
+    ByteLevel(use_regex=false)], post-processor Sequence[ByteLevel, TemplateProcessing] that puts
+    ``<|begin_of_text|>`` in front, ``ignore_merges`` as given, and ``n_added`` added tokens
+    (``<|begin_of_text|>``, ``<|end_of_text|>`` and reserved specials) after the ``vocab_size``
+    model entries, as Llama-3 lays them out. The stand-in for Llama-3 / cl100k_base / Qwen2, which
+    cannot be downloaded here; the counts differ from theirs, the work per byte is of the same kind."""
+    if os.path.isfile(path):
+        return path
+    from tokenizers import Regex, Tokenizer, decoders, models, pre_tokenizers, processors, trainers
+
+    from ..utils import synth
+
+    pat = {"A": SPLIT_PATTERN_A, "B": SPLIT_PATTERN_B}[pattern]
+    texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
+    tok = Tokenizer(models.BPE(ignore_merges=ignore_merges))
+    tok.pre_tokenizer = pre_tokenizers.Sequence([
+        pre_tokenizers.Split(Regex(pat), behavior="isolated", invert=False),
+        pre_tokenizers.ByteLevel(add_prefix_space=False, use_regex=False)])
+    tok.decoder = decoders.ByteLevel()
+    tr = trainers.BpeTrainer(vocab_size=vocab_size, special_tokens=[], show_progress=False,
+                             initial_alphabet=pre_tokenizers.ByteLevel.alphabet())
+    tok.train_from_iterator(texts, tr)
+    special = ["<|begin_of_text|>", "<|end_of_text|>"][:n_added]
+    special += [f"<|reserved_special_token_{i}|>" for i in range(n_added - len(special))]
+    tok.add_special_tokens(special)
+    procs = [processors.ByteLevel(trim_offsets=False)]
+    if special:
+        procs.append(processors.TemplateProcessing(
+            single="<|begin_of_text|> $A", pair="<|begin_of_text|> $A <|begin_of_text|>:1 $B:1",
+            special_tokens=[("<|begin_of_text|>", tok.token_to_id("<|begin_of_text|>"))]))
+    tok.post_processor = processors.Sequence(procs)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f"{path}.{os.getpid()}.tmp"
     tok.save(tmp)

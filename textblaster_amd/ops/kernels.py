@@ -160,7 +160,9 @@ PRE_TILE = 16384  # kernels.hip kPreTile
 class DevBpe(ctypes.Structure):
     """csrc/common/bpe.h DevBpe (checked against tb_sizeof_bpe)."""
     _fields_ = [("byte_id", _P), ("keys", _P), ("vals", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
-                ("mask", _U32), ("n_added", _I32), ("added_off", _I32 * 9), ("post_add", _I32)]
+                ("mask", _U32), ("n_added", _I32), ("added_off", _I32 * 9), ("post_add", _I32),
+                ("aoff", _P), ("vslots", _P), ("vpool", _P), ("amask", ctypes.c_uint64 * 4),
+                ("vmask", _U32), ("vlongest", _I32), ("kind", _I32), ("ignore_merges", _I32)]
 
 
 class BpeTables:
@@ -172,15 +174,32 @@ class BpeTables:
 
         self.arrays = [hiprt.to_device(a) for a in (spec.byte_id, spec.keys, spec.vals, cls_tables[0], cls_tables[1],
                                                     spec.added)]
-        if len(spec.added_off) > 9:
+        split = spec.kind != 0
+        if len(spec.added_off) > (1025 if split else 9):
             raise DeviceError("bpe: too many added tokens")
         st = DevBpe()
         st.byte_id, st.keys, st.vals, st.cls1, st.cls2, st.added = [a.data_ptr() for a in self.arrays]
         st.mask = spec.mask
         st.n_added = max(len(spec.added_off) - 1, 0)
-        for i, v in enumerate(spec.added_off):
-            st.added_off[i] = v
         st.post_add = spec.post_add
+        st.kind = spec.kind
+        if not split:
+            for i, v in enumerate(spec.added_off):
+                st.added_off[i] = v
+        else:
+            # the split-regex family: the added tokens' offsets and the vocabulary table in HBM
+            if spec.added_off and (spec.added_off[-1] > len(spec.added) or spec.added_mask is None):
+                raise DeviceError("bpe: added-token buffers")
+            self.arrays.append(hiprt.to_device(np.array(spec.added_off or [0], dtype=np.int32)))
+            st.aoff = self.arrays[-1].data_ptr()
+            for i in range(4):
+                st.amask[i] = int(spec.added_mask[i]) if spec.added_off else 0
+            if spec.ignore_merges:
+                if spec.vslots is None or len(spec.vslots) != 2 * (spec.vmask + 1) or spec.vlongest < 1:
+                    raise DeviceError("bpe: vocabulary table shape")
+                self.arrays += [hiprt.to_device(spec.vslots), hiprt.to_device(spec.vpool)]
+                st.vslots, st.vpool = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
+                st.vmask, st.vlongest, st.ignore_merges = spec.vmask, spec.vlongest, 1
         self.struct = st
 
 
@@ -460,8 +479,9 @@ class Kernels:
         return BpeTables(spec, native.host().bpe_classes())
 
     def bpe_count(self, tabs: BpeTables, text, off, n_dev, n_max: int, counts):
-        """k_bpe_count: token counts of documents k < min(n_dev[0], n_max) (csrc/hip/bpe.hip);
-        ``n_dev``: optional one-element int64 device array (the kept count of K16)."""
+        """k_bpe_count + k_bpe_long, or k_bpe_split_count + k_bpe_split_long for a split-regex spec:
+        token counts of documents k < min(n_dev[0], n_max) (csrc/hip/bpe.hip); ``n_dev``: optional
+        one-element int64 device array (the kept count of K16)."""
         if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
             raise DeviceError("bpe_count: operand shapes")
         rc = self.lib.tb_bpe_count(self.stream(), ctypes.byref(tabs.struct), text.data_ptr(), off.data_ptr(),
@@ -491,7 +511,7 @@ class Kernels:
         return self.wp_tables(spec) if isinstance(spec, WordPieceSpec) else self.bpe_tables(spec)
 
     def token_count(self, tabs, text, off, n_dev, n_max: int, counts):
-        """k_wp_count or k_bpe_count, by the kind of ``tabs``."""
+        """k_wp_count, k_bpe_count or k_bpe_split_count, by the kind of ``tabs``."""
         fn = self.wp_count if isinstance(tabs, WpTables) else self.bpe_count
         fn(tabs, text, off, n_dev, n_max, counts)
 

@@ -172,9 +172,10 @@ class Engine:
         self._bw_lock = threading.Lock()
         self._bw_nolist = set()
         self.device_runner = None
-        # trailing TokenCounter steps (after every filter) whose tokenizer is a byte-level BPE or a
-        # BERT-style WordPiece are counted by the device path on the kept outputs (k_bpe_count /
-        # k_wp_count); the others on the host
+        # trailing TokenCounter steps (after every filter) whose tokenizer is a byte-level BPE (GPT-2's
+        # ByteLevel regex, or the Llama-3 / cl100k_base / Qwen2 Split patterns) or a BERT-style
+        # WordPiece are counted by the device path on the kept outputs (k_bpe_count /
+        # k_bpe_split_count / k_wp_count); the others on the host
         from .device import trailing_token_counters
 
         self._trailing_tc = set(trailing_token_counters(self.plan))
@@ -675,9 +676,9 @@ class Engine:
             rec = np.full(ndocs, -1, dtype=np.int64)
             if len(alive) and resolved is not None and resolved.n_kept_final() == len(alive):
                 # K16 agreed: final kept output k is alive[k]; its count came from k_bpe_count /
-                # k_wp_count (or -2: added-token text, a BPE pre-token over 2048 bytes, WordPiece
-                # text the normalizer changes beyond ASCII case -> the tokenizer, like unsupported
-                # tokenizers)
+                # k_bpe_split_count / k_wp_count (or -2: added-token text, a BPE pre-token over 2048
+                # bytes, WordPiece text the normalizer changes beyond ASCII case -> the tokenizer, like
+                # unsupported tokenizers)
                 dev = resolved.kept_tokens(i)
                 cnt = dev.astype(np.int64) if dev is not None else np.full(len(alive), -2, np.int64)
                 bad = np.nonzero(cnt < 0)[0]
