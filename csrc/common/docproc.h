@@ -112,7 +112,7 @@ struct PHView {
 };
 
 // a very long document's code points and UAX#29 word-break marks, computed before
-// its stage workgroup runs by many workgroups at once (kernels.hip k_pre_count / k_pre_decode /
+// its stage workgroup runs by many workgroups at once (prepass.hip k_pre_count / k_pre_decode /
 // k_pre_wb): the non-packed Cps layout (documents of 64 KiB and more) plus the marks words()
 // would compute.
 struct PreDoc {
@@ -141,7 +141,7 @@ struct PreDoc {
   uint32_t W;
   uint32_t pad;
   // GopherRepetition's word arrays (gopher_rep_record) built by many workgroups
-  // (kernels.hip k_pre_wcanon): word hashes, the canonicalisation table (1.5 W + 2 64-bit slots)
+  // (prepass.hip k_pre_wcanon): word hashes, the canonicalisation table (1.5 W + 2 64-bit slots)
   // and each word's slot, per-2048-word chunk sums and bases, and the results wid / WL / K / PB
   // (W + 1 entries each); wready = 1 once they are filled.
   uint64_t* wh;

@@ -1,4 +1,4 @@
-"""K18 on the GPU: k_meta_size / k_meta_write (csrc/hip/kernels.hip) against their host emulation
+"""K18 on the GPU: k_meta_size / k_meta_write (csrc/hip/resolve.hip) against their host emulation
 over the record matrices of tests/meta_matrix.py, and the DeviceRunner's metadata column against
 BatchState.assemble over the records it downloaded. Needs an MI355X."""
 import dataclasses
@@ -17,7 +17,7 @@ from textblaster_amd.utils import metrics, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-LDS_SLICE = 260  # kernels.hip kMetaSlice: longer rows are written straight to the column
+LDS_SLICE = 260  # resolve.hip kMetaSlice: longer rows are written straight to the column
 
 
 @pytest.fixture(scope="module")

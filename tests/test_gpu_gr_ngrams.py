@@ -10,7 +10,7 @@ from textblaster_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
 
-# word capacities of the k_gr_ngrams instantiations (csrc/hip/kernels.hip, launch_gr_ngrams)
+# word capacities of the k_gr_ngrams instantiations (csrc/hip/gr_ngrams.hip, launch_gr_ngrams)
 MAXW = (256, 512, 1024)
 
 

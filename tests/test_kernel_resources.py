@@ -17,8 +17,8 @@ def test_hot_kernels_within_register_budget():
 
     if not os.path.exists(native.RESOURCES_JSON):
         pytest.skip("no resource report: run __graft_entry__.build() first")
-    if os.path.getmtime(native.RESOURCES_JSON) < os.path.getmtime(os.path.join(ROOT, "csrc/hip/kernels.hip")):
-        pytest.skip("resource report older than kernels.hip: rebuild")
+    if os.path.getmtime(native.RESOURCES_JSON) < native._newest(native._sources("hip", ".hip") + native._headers()):
+        pytest.skip("resource report older than the kernel sources or headers: rebuild")
     rep = json.load(open(native.RESOURCES_JSON))
     budget = {k: v for k, v in json.load(open(os.path.join(ROOT, "csrc/hip/resource_budget.json"))).items()
               if not k.startswith("_")}

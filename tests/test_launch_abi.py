@@ -1,4 +1,4 @@
-"""The C launch ABI of libtbhip.so (csrc/hip/kernels.hip extern "C" block) against its ctypes
+"""The C launch ABI of libtbhip.so (the extern "C" blocks of the csrc/hip/*.hip kernel units) against its ctypes
 mirror (ops/kernels.py): struct sizes, and the launchers' argument checks, which all return before
 any HIP call, so these run without a GPU."""
 import ctypes

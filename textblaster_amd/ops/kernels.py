@@ -1,4 +1,4 @@
-"""ctypes bindings for libtbhip.so (csrc/hip/kernels.hip, html.hip, runtime.hip) and thin launch
+"""ctypes bindings for libtbhip.so (the kernel units of csrc/hip/, html.hip, runtime.hip) and thin launch
 helpers.
 
 Device memory comes from the native runtime layer (ops/hiprt.py: caching HBM allocator,
@@ -6,7 +6,7 @@ Device memory comes from the native runtime layer (ops/hiprt.py: caching HBM all
 launch checks the returned hipError_t and raises — there is no silent fallback on a GPU box.
 
 The argument groups the document kernels share travel as structs (``LAUNCH_STRUCTS``: each the one
-mirror of its C struct at the head of kernels.hip's extern "C" block, sizes checked when
+mirror of its C struct in csrc/hip/kernel_common.h or its family's unit, sizes checked when
 ``Kernels`` is created): ``Tables`` per batch, ``Docs`` and ``Work`` per launch, ``DictIn`` /
 ``DictLines`` per content version / C4 step. ``_SIGS`` types them as ``POINTER(Struct)``, so a
 struct in the wrong place raises in Python.
@@ -153,8 +153,8 @@ PRE_DOC = np.dtype([("off", "<u8"), ("prop", "<u8"), ("wbm", "<u8"), ("nl_pos", 
                     ("wbs", "<u8"), ("wbe", "<u8"), ("wal", "<u8"), ("W", "<u4"), ("pad", "<u4"),
                     ("wh", "<u8"), ("wtab", "<u8"), ("wk", "<u8"), ("wpb", "<u8"), ("wcsum", "<u8"),
                     ("wslot", "<u8"), ("wid", "<u8"), ("wl", "<u8"), ("wready", "<u4"), ("pad2", "<u4")])
-PRE_WCHUNK = 2048  # kernels.hip kPreWChunk
-PRE_TILE = 16384  # kernels.hip kPreTile
+PRE_WCHUNK = 2048  # prepass.hip kPreWChunk
+PRE_TILE = 16384  # prepass.hip kPreTile
 
 
 class DevBpe(ctypes.Structure):

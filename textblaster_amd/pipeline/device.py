@@ -611,7 +611,7 @@ class DeviceRunner:
         # documents longer than this run one workgroup (4 waves) each instead of one wave
         self.long_doc_bytes = tu.long_doc_bytes
         # three long-document workgroups per CU (with the register budget of k_stage_analyze_blk,
-        # csrc/hip/kernels.hip TB_BLK_WPE)
+        # csrc/hip/stage.hip TB_BLK_WPE)
         self.lds_bytes_blk = tu.lds_bytes_blk
         self.block_threads = int(self.k.lib.tb_block_threads())  # threads of the long-document workgroups
         # LDS slice of the split-order workgroups (k_gr_dup_split)

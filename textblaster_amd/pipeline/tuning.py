@@ -9,7 +9,7 @@ Every field has a measured default; an operator overrides them with ONE environm
 a typo never silently measures the default. The A/B evidence behind each default is cited next to
 its field; README.md "Tuning" lists them.
 
-Compile-time budgets (waves per EU of each kernel, ``TB_*_WPE`` in csrc/hip/kernels.hip) are not
+Compile-time budgets (waves per EU of each kernel, ``TB_*_WPE`` in the csrc/hip/*.hip kernel units) are not
 runtime knobs: tools/build_variant.sh builds an A/B library and ``TB_HIP_LIB`` loads it.
 """
 from __future__ import annotations

@@ -1,5 +1,6 @@
 """Per-kernel register / scratch / occupancy report of the gfx950 build (from the compiler's
 assembly comments): python tools/kernel_resources.py [extra hipcc flags...]"""
+import glob
 import os
 import re
 import subprocess
@@ -13,9 +14,9 @@ def main():
     flags = sys.argv[1:]
     text = ""
     with tempfile.TemporaryDirectory() as d:
-        for src in ("kernels.hip", "bpe.hip", "wordpiece.hip", "html.hip"):
+        for src in sorted(glob.glob(os.path.join(ROOT, "csrc/hip", "*.hip"))):
             subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--offload-device-only",
-                            "-S", *flags, os.path.join(ROOT, "csrc/hip", src), "-o", os.path.join(d, "k.s")],
+                            "-S", *flags, src, "-o", os.path.join(d, "k.s")],
                            check=True)
             text += open(os.path.join(d, "k.s")).read()
     cur = None
