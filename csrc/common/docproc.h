@@ -4,6 +4,9 @@
 //
 //   decode          UTF-8 -> code point byte offsets + 16-bit properties  (reference: chars())
 //   prefix_hash8    PH8[k] = H(bytes[0..8k)): any substring hash is <= 14 Horner steps + 1 power
+//                   (readers: dup_spans and the word hashes of the workgroup kernels and the host
+//                   emulation; in the one-wave kernel only the in-stage word hashes, so it skips
+//                   the pass when the n-gram kernels take the words: analyze_stage, need_ph)
 //   words           UAX#29 word segments, trimmed, kept iff they contain a non-PUNCTUATION,
 //                   non-whitespace char; break bitmask + one fused scan/compaction pass
 //                                                       (reference utils/text.rs:103-181)
@@ -921,7 +924,73 @@ TB_HD bool bytes_eq(const uint8_t* b, uint32_t a0, uint32_t a1, uint32_t b0, uin
   return diff == 0;
 }
 
+// Table key of a byte span taken from the span itself: its length and its first and last
+// min(8, len) bytes (spans of up to 16 bytes are covered whole). Equal spans get equal keys; unequal
+// spans with one key only cost a byte comparison.
+TB_HD uint64_t span_ends_key(const uint8_t* b, uint32_t s, uint32_t e) {
+  const uint32_t len = e - s, m = len < 8u ? len : 8u;
+  uint64_t head = 0, tail = 0;
+  for (uint32_t k = 0; k < m; ++k) {
+    head |= (uint64_t)b[s + k] << (8u * k);
+    tail |= (uint64_t)b[e - m + k] << (8u * k);
+  }
+  return dev_key(head ^ (tail * kHashBase), len);
+}
+
+#if defined(__HIPCC__)
+// dup_spans of a one-wave document with at most 64 spans: lane j keeps span j's start, length and
+// first min(8, len) bytes in registers, and a uniform loop over i broadcasts span i to the lanes
+// j > i. A lane that is still its own canonical element and has the same length and first bytes
+// compares the rest of the bytes and, if they are equal, becomes a repeat of i. i only grows, so
+// the first hit is the smallest equal index (canonicalize's definition), and an i that is itself a
+// repeat is skipped: its equals were taken by its canonical element. No table, no canon[] array,
+// no allocation. Every lane read and ballot sits in wave-uniform control flow (wb_pair_dword's
+// rule); only the byte comparison runs divergent.
+template <class P, class SpanF>
+__device__ __forceinline__ void dup_spans_lanes(DocCtx<P>& x, const uint8_t* b, uint32_t n, SpanF&& span,
+                                                int64_t* out_elems, int64_t* out_bytes) {
+  const uint32_t lane = x.par.lane;
+  uint32_t s = 0, len = 0, lo = 0, hi = 0;
+  if (lane < n) {
+    uint32_t e;
+    span(lane, s, e);
+    len = e - s;
+    const uint32_t m = len < 8u ? len : 8u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      if (k < m) lo |= (uint32_t)b[s + k] << (8u * k);
+      if (k + 4 < m) hi |= (uint32_t)b[s + k + 4] << (8u * k);
+    }
+  }
+  uint64_t dup = 0;  // bit j: span j repeats an earlier one (uniform)
+  for (uint32_t i = 0; i + 1 < n; ++i) {
+    if ((dup >> i) & 1ull) continue;
+    const uint32_t si = (uint32_t)__builtin_amdgcn_readlane((int)s, (int)i);
+    const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)len, (int)i);
+    const uint32_t loi = (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)i);
+    const uint32_t hii = (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)i);
+    bool hit = lane > i && lane < n && !((dup >> lane) & 1ull) && len == li && lo == loi && hi == hii;
+    // The first 8 bytes are the signature: equal already. A plain byte loop, not bytes_eq: its
+    // 16 loads in flight per side, inlined at the three call sites next to the table path's own
+    // copy, took the kernel from 128 to 141 spilled VGPRs.
+    if (hit) {
+      uint32_t diff = 0;
+#pragma unroll 1
+      for (uint32_t k = 8; k < li; ++k) diff |= (uint32_t)(b[si + k] ^ b[s + k]);
+      hit = diff == 0;
+    }
+    dup |= __ballot(hit);
+  }
+  *out_elems = (int64_t)__popcll(dup);
+  *out_bytes = (int64_t)x.par.template wave_sum<uint32_t>(((dup >> lane) & 1ull) ? len : 0u);
+}
+#endif
+
 // find_duplicates over byte spans [s[i], e[i]): (#repeats, sum of repeat byte lengths).
+// The prefix hashes `ph` key the table of the workgroup kernels and of the host emulation. A
+// one-wave document never reads them: up to 64 spans are compared lane against lane
+// (dup_spans_lanes), more go through the same table keyed by the spans' own ends (span_ends_key).
+// The key decides nothing either way: every table hit is verified by bytes_eq.
 template <class P, class SpanF>
 TB_HD void dup_spans(DocCtx<P>& x, const uint8_t* b, const PHView& ph, uint32_t n, SpanF&& span,
                      int64_t* out_elems, int64_t* out_bytes) {
@@ -930,6 +999,14 @@ TB_HD void dup_spans(DocCtx<P>& x, const uint8_t* b, const PHView& ph, uint32_t 
     *out_bytes = 0;
     return;
   }
+#if defined(__HIPCC__)
+  if constexpr (P::kWaves == 1) {
+    if (n <= 64) {
+      dup_spans_lanes(x, b, n, span, out_elems, out_bytes);
+      return;
+    }
+  }
+#endif
   const auto mark = x.mark();
   uint32_t* canon = x.template alloc_hot<uint32_t>(n + 1);
   if (x.overflow) return;
@@ -938,7 +1015,8 @@ TB_HD void dup_spans(DocCtx<P>& x, const uint8_t* b, const PHView& ph, uint32_t 
       [&](uint32_t i) {
         uint32_t s, e;
         span(i, s, e);
-        return dev_key(span_hash8(x, ph, s, e), e - s);
+        if constexpr (P::kWaves == 1) return span_ends_key(b, s, e);
+        else return dev_key(span_hash8(x, ph, s, e), e - s);
       },
       [&](uint32_t i, uint32_t j) {
         uint32_t s0, e0, s1, e1;
@@ -1377,7 +1455,10 @@ TB_HD uint32_t count_sentences_upto(DocCtx<P>& x, const Cps& c, uint32_t s, uint
   return cnt;
 }
 
-template <class P>
+// kExport (one-wave kernel): the build for launches with an export (split mode, one GopherRepetition
+// step with n-gram orders): the n-gram kernels compute every order, so the in-stage n-gram code is
+// compiled out of it.
+template <class P, bool kExport = false>
 TB_HD void gopher_rep_record(DocCtx<P>& x, const DevStep& ds, const uint8_t* b, const Cps& c,
                              const PHView& ph, const Words& w, int64_t* r, bool release_props = false,
                              GrExport* ex = nullptr, const PreDoc* pre = nullptr,
@@ -1511,7 +1592,14 @@ TB_HD void gopher_rep_record(DocCtx<P>& x, const DevStep& ds, const uint8_t* b, 
       x.set_flag(DOC_NEEDS_CPU);
       return;
     }
-    if (ngrams && ex) {
+    if constexpr (kExport) {
+      // (the launcher picks this build only with an export; anything else goes to the exact CPU path)
+      if (!(ngrams && ex)) {
+        x.set_flag(DOC_NEEDS_CPU);
+        return;
+      }
+    }
+    if (kExport || (ngrams && ex)) {
       // One-wave documents in split mode: the n-gram kernels rebuild everything word-level (ids,
       // byte prefix, concatenation hashes) from the word spans and the text, so nothing is hashed
       // or canonicalised here and only the spans are exported. (Nothing is allocated after this
@@ -1532,202 +1620,204 @@ TB_HD void gopher_rep_record(DocCtx<P>& x, const DevStep& ds, const uint8_t* b, 
       return;
     }
   }
-  uint32_t* wid = nullptr;
-  uint32_t* WL = nullptr;
-  uint64_t* K = nullptr;
-  uint64_t* PB = nullptr;
-  if (ngrams && pre && pre->wready) {
-    // built by many workgroups before this one (k_pre_wcanon); a hash collision between unequal
-    // words has flagged the document for the CPU path there
-    wid = pre->wid;
-    WL = pre->wl;
-    K = pre->wk;
-    PB = pre->wpb;
-  } else if (ngrams) {
-    // LDS only while a canonicalisation table for W elements (~6 W bytes) still fits next to them
-    // (split mode: HBM, they outlive this kernel)
-    const uint64_t tab_bytes = 6ull * W + 64;
-    wid = ex ? x.template alloc<uint32_t>(W + 1) : x.template alloc_hot_keep<uint32_t>(W + 1, tab_bytes);
-    WL = ex ? x.template alloc<uint32_t>(W + 1) : x.template alloc_hot_keep<uint32_t>(W + 1, tab_bytes);
-    K = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
-    PB = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
-    const auto mw = x.mark();
-    uint64_t* wh = x.template alloc_hot_hi<uint64_t>(W + 1);
-    if (x.overflow) return;
-    x.par.for_n(W, [&](uint32_t k) { wh[k] = span_hash8(x, ph, w.bs[k], w.be[k]); });
-    x.par.sync();
-    x.stamp(PH_GR_WH);
-    canonicalize(
-        x, W, [&](uint32_t k) { return dev_key(wh[k], w.be[k] - w.bs[k]); },
-        [&](uint32_t i, uint32_t j) { return bytes_eq<P>(b, w.bs[i], w.be[i], w.bs[j], w.be[j]); }, wid);
-    x.stamp(PH_GR_WCANON);
-    const uint32_t totl = x.par.template scan<uint32_t>(
-        W, 0u, [](uint32_t a, uint32_t c2) { return a + c2; },
-        [&](uint32_t k) { return w.be[k] - w.bs[k]; }, [&](uint32_t k, uint32_t e) { WL[k] = e; });
-    x.par.single([&]() { WL[W] = totl; });
-    x.par.sync();
-    x.par.for_n(W + 1, [&](uint32_t k) { PB[k] = x.powb(WL[k]); });
-    const uint64_t ktot = x.par.template scan<uint64_t>(
-        W, 0ull, [](uint64_t a, uint64_t c2) { return a + c2; },
-        [&](uint32_t j) { return wh[j] * x.ipowb(WL[j + 1]); }, [&](uint32_t k, uint64_t e) { K[k] = e; });
-    x.par.single([&]() { K[W] = ktot; });
-    x.par.sync();
-    x.reset(mw);  // wh
-    if (x.overflow) return;
-  }
-  x.stamp(PH_GR_WORDS);
-  // the n-gram statistics read words, bytes and the arrays above only: the top of the LDS slice
-  // (code point arrays, prefix hashes) goes to their hash tables
-  if (release_props) x.release_hi();
-  if (ngrams) {
-    const DupGrams dg{wid, WL, K, PB, w.bs, w.be, b};
-    // Top n-grams (space-joined grams: equal iff their word sequences are equal). Canonical ids
-    // of the n-grams are built incrementally: the n-gram at p is the pair (id of the (n-1)-gram
-    // at p, id of word p+n-1), so each order is one exact pair canonicalisation (O(1) equality,
-    // no hashing of the gram text).
-    if (ds.n_top > 0 && ex) {
-      // split mode: k_gr_dup_split computes each top order in its own workgroup
-      x.par.single([&]() { for (int t = 0; t < ds.n_top; ++t) r[rec_gr_fixed() + t] = 0; });
-    } else if (ds.n_top > 0) {
-      int max_top = 0;
-      for (int t = 0; t < ds.n_top; ++t) max_top = ds.top_n[t] > max_top ? ds.top_n[t] : max_top;
-      const auto m2 = x.mark();
-      // two id arrays in turn; the counts of order n go to the one the (n-1)-gram ids used
-      uint32_t* ga = x.template alloc_hot_keep<uint32_t>(W + 1, 6ull * W + 64);
-      uint32_t* gb = x.template alloc_hot_keep<uint32_t>(W + 1, 6ull * W + 64);
+  if constexpr (!kExport) {
+    uint32_t* wid = nullptr;
+    uint32_t* WL = nullptr;
+    uint64_t* K = nullptr;
+    uint64_t* PB = nullptr;
+    if (ngrams && pre && pre->wready) {
+      // built by many workgroups before this one (k_pre_wcanon); a hash collision between unequal
+      // words has flagged the document for the CPU path there
+      wid = pre->wid;
+      WL = pre->wl;
+      K = pre->wk;
+      PB = pre->wpb;
+    } else if (ngrams) {
+      // LDS only while a canonicalisation table for W elements (~6 W bytes) still fits next to them
+      // (split mode: HBM, they outlive this kernel)
+      const uint64_t tab_bytes = 6ull * W + 64;
+      wid = ex ? x.template alloc<uint32_t>(W + 1) : x.template alloc_hot_keep<uint32_t>(W + 1, tab_bytes);
+      WL = ex ? x.template alloc<uint32_t>(W + 1) : x.template alloc_hot_keep<uint32_t>(W + 1, tab_bytes);
+      K = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
+      PB = ex ? x.template alloc<uint64_t>(W + 1) : x.template alloc_hot_keep<uint64_t>(W + 1, tab_bytes);
+      const auto mw = x.mark();
+      uint64_t* wh = x.template alloc_hot_hi<uint64_t>(W + 1);
       if (x.overflow) return;
-      x.par.single([&]() { for (int t = 0; t < ds.n_top; ++t) r[rec_gr_fixed() + t] = 0; });
-      const uint32_t* gprev = wid;
-      for (uint32_t n = 1; n <= (uint32_t)max_top && W >= n; ++n) {
-        const uint32_t G = W - n + 1;
-        const uint32_t* gc = wid;
-        uint32_t* cnt = (n == 1 || !(n & 1)) ? ga : gb;
-        if (n > 1) {
-          uint32_t* gcur = (n & 1) ? ga : gb;
-          canonicalize(
-              x, G, [&](uint32_t p) { return mix64(((uint64_t)gprev[p] << 32) ^ (uint64_t)wid[p + n - 1] ^ ((uint64_t)n << 60)); },
-              [&](uint32_t p, uint32_t q) { return gprev[p] == gprev[q] && wid[p + n - 1] == wid[q + n - 1]; }, gcur);
-          gc = gcur;
-          gprev = gcur;
-          x.stamp(PH_GR_TOP_CANON);
-        }
-        bool wanted = false;
-        for (int t = 0; t < ds.n_top; ++t) wanted |= ds.top_n[t] == (int32_t)n;
-        if (!wanted) continue;
-        x.par.for_n(G, [&](uint32_t p) { cnt[p] = 0; });
-        x.par.sync();
-        x.par.for_n(G, [&](uint32_t p) { P::add32(&cnt[gc[p]], 1u); });
-        x.par.sync();
-        const uint32_t maxc = x.par.template max<uint32_t>(G, 0u, [&](uint32_t p) { return cnt[p]; });
-        int64_t v = 0;
-        if (maxc > 1) {
-          const uint32_t maxlen = x.par.template max<uint32_t>(G, 0u, [&](uint32_t p) {
-            return cnt[p] == maxc ? (WL[p + n] - WL[p] + n - 1) : 0u;
-          });
-          v = (int64_t)maxlen * (int64_t)maxc;
-        }
-        x.par.single([&]() {
-          for (int t = 0; t < ds.n_top; ++t) if (ds.top_n[t] == (int32_t)n) r[rec_gr_fixed() + t] = v;
-        });
-        x.par.sync();
-      }
-      x.reset(m2);
+      x.par.for_n(W, [&](uint32_t k) { wh[k] = span_hash8(x, ph, w.bs[k], w.be[k]); });
+      x.par.sync();
+      x.stamp(PH_GR_WH);
+      canonicalize(
+          x, W, [&](uint32_t k) { return dev_key(wh[k], w.be[k] - w.bs[k]); },
+          [&](uint32_t i, uint32_t j) { return bytes_eq<P>(b, w.bs[i], w.be[i], w.bs[j], w.be[j]); }, wid);
+      x.stamp(PH_GR_WCANON);
+      const uint32_t totl = x.par.template scan<uint32_t>(
+          W, 0u, [](uint32_t a, uint32_t c2) { return a + c2; },
+          [&](uint32_t k) { return w.be[k] - w.bs[k]; }, [&](uint32_t k, uint32_t e) { WL[k] = e; });
+      x.par.single([&]() { WL[W] = totl; });
+      x.par.sync();
+      x.par.for_n(W + 1, [&](uint32_t k) { PB[k] = x.powb(WL[k]); });
+      const uint64_t ktot = x.par.template scan<uint64_t>(
+          W, 0ull, [](uint64_t a, uint64_t c2) { return a + c2; },
+          [&](uint32_t j) { return wh[j] * x.ipowb(WL[j + 1]); }, [&](uint32_t k, uint64_t e) { K[k] = e; });
+      x.par.single([&]() { K[W] = ktot; });
+      x.par.sync();
+      x.reset(mw);  // wh
+      if (x.overflow) return;
     }
-    x.stamp(PH_GR_TOP);
-    if (ex) {
-      // split mode: export the word arrays; k_gr_dup_split finishes every order (top and
-      // duplicated) in its own workgroup and writes the n-gram fields
-      const uint64_t base = (x.used + 255) & ~255ull;
-      x.par.single([&]() {
-        for (int t = 0; t < ds.n_dup; ++t) r[rec_gr_fixed() + ds.n_top + t] = 0;
-        ex->wid = wid; ex->WL = WL; ex->K = K; ex->PB = PB; ex->bs = w.bs; ex->be = w.be;
-        ex->b = b_export ? b_export : b;
-        ex->free_base = x.scr + base;
-        ex->free_cap = x.cap > base ? x.cap - base : 0;
-        ex->W = W;
-        ex->valid = x.overflow ? 0u : 1u;
-      });
-      x.par.sync();
-    } else if (ds.n_dup > 0) {
-      // Two phases over all requested orders n (reference find_all_duplicate,
-      // utils/text.rs:241-259):
-      //   1. per n: canonicalise the n-gram concatenations into gc_n (exact: hash groups, then
-      //      word-id / byte equality) and mark repeated positions in R_n (p with gc[p] != p, and
-      //      their first occurrence gc[p]);
-      //   2. the greedy walks of all orders run at once, one lane each (they are independent
-      //      and sequential, so n walks cost about the longest one instead of their sum).
-      // Arrays of all orders are packed back to back: gc_n at gbase(t), bitmaps at t * 2 * SW.
-      const uint32_t SW = (W + 31) / 32 + 1;
-      const int nd = ds.n_dup;
-      auto gsize = [&](int t) -> uint32_t {
-        const uint32_t n = (uint32_t)ds.dup_n[t];
-        return (n == 0 || W < n) ? 0u : W - n + 1;
-      };
-      uint32_t gtot = 0;
-      for (int t = 0; t < nd; ++t) gtot += gsize(t);
-      const auto m3 = x.mark();
-      uint32_t* bits = x.template alloc_hot<uint32_t>(2 * (uint64_t)SW * (uint64_t)nd);  // [sn | R] per order
-      // wave documents keep the canonical ids in 16 bits (half the slice; W < kWave16)
-      using GcT = std::conditional_t<P::kWaves == 1, uint16_t, uint32_t>;
-      GcT* gcall = x.template alloc_hot_keep<GcT>((uint64_t)gtot + 1, 6ull * W + 64);
-      if (x.overflow) return;
-      x.par.for_n(2 * SW * (uint32_t)nd, [&](uint32_t i) { bits[i] = 0; });
-      x.par.sync();
-      uint32_t gb = 0;
-      for (int t = 0; t < nd; ++t) {
-        const uint32_t n = (uint32_t)ds.dup_n[t];
-        const uint32_t G = gsize(t);
-        if (G == 0) continue;
-        GcT* gc = gcall + gb;
-        uint32_t* R = bits + (uint32_t)t * 2 * SW + SW;
-        gb += G;
-        auto mark_rep = [&](uint32_t p, uint32_t g) {
-          if (g != p) {  // repeated: the position and its first occurrence
-            P::or32(&R[p >> 5], 1u << (p & 31));
-            P::or32(&R[g >> 5], 1u << (g & 31));
+    x.stamp(PH_GR_WORDS);
+    // the n-gram statistics read words, bytes and the arrays above only: the top of the LDS slice
+    // (code point arrays, prefix hashes) goes to their hash tables
+    if (release_props) x.release_hi();
+    if (ngrams) {
+      const DupGrams dg{wid, WL, K, PB, w.bs, w.be, b};
+      // Top n-grams (space-joined grams: equal iff their word sequences are equal). Canonical ids
+      // of the n-grams are built incrementally: the n-gram at p is the pair (id of the (n-1)-gram
+      // at p, id of word p+n-1), so each order is one exact pair canonicalisation (O(1) equality,
+      // no hashing of the gram text).
+      if (ds.n_top > 0 && ex) {
+        // split mode: k_gr_dup_split computes each top order in its own workgroup
+        x.par.single([&]() { for (int t = 0; t < ds.n_top; ++t) r[rec_gr_fixed() + t] = 0; });
+      } else if (ds.n_top > 0) {
+        int max_top = 0;
+        for (int t = 0; t < ds.n_top; ++t) max_top = ds.top_n[t] > max_top ? ds.top_n[t] : max_top;
+        const auto m2 = x.mark();
+        // two id arrays in turn; the counts of order n go to the one the (n-1)-gram ids used
+        uint32_t* ga = x.template alloc_hot_keep<uint32_t>(W + 1, 6ull * W + 64);
+        uint32_t* gb = x.template alloc_hot_keep<uint32_t>(W + 1, 6ull * W + 64);
+        if (x.overflow) return;
+        x.par.single([&]() { for (int t = 0; t < ds.n_top; ++t) r[rec_gr_fixed() + t] = 0; });
+        const uint32_t* gprev = wid;
+        for (uint32_t n = 1; n <= (uint32_t)max_top && W >= n; ++n) {
+          const uint32_t G = W - n + 1;
+          const uint32_t* gc = wid;
+          uint32_t* cnt = (n == 1 || !(n & 1)) ? ga : gb;
+          if (n > 1) {
+            uint32_t* gcur = (n & 1) ? ga : gb;
+            canonicalize(
+                x, G, [&](uint32_t p) { return mix64(((uint64_t)gprev[p] << 32) ^ (uint64_t)wid[p + n - 1] ^ ((uint64_t)n << 60)); },
+                [&](uint32_t p, uint32_t q) { return gprev[p] == gprev[q] && wid[p + n - 1] == wid[q + n - 1]; }, gcur);
+            gc = gcur;
+            gprev = gcur;
+            x.stamp(PH_GR_TOP_CANON);
           }
-        };
-        if constexpr (P::kWaves != 1) {
-          // fused into the canonicalisation's last pass
-          canonicalize_res(
-              x, G, [&](uint32_t p) { return dg.key(p, n); }, [&](uint32_t p, uint32_t q) { return dg.eq(p, q, n); },
-              gc, mark_rep);
-          x.stamp(PH_GR_DUP_CANON);
-        } else {
-          // own pass in the one-wave kernel (the fused form costs it registers)
-          canonicalize(
-              x, G, [&](uint32_t p) { return dg.key(p, n); }, [&](uint32_t p, uint32_t q) { return dg.eq(p, q, n); },
-              gc);
-          x.stamp(PH_GR_DUP_CANON);
-          x.par.for_n(G, [&](uint32_t p) { mark_rep(p, gc[p]); });
+          bool wanted = false;
+          for (int t = 0; t < ds.n_top; ++t) wanted |= ds.top_n[t] == (int32_t)n;
+          if (!wanted) continue;
+          x.par.for_n(G, [&](uint32_t p) { cnt[p] = 0; });
+          x.par.sync();
+          x.par.for_n(G, [&](uint32_t p) { P::add32(&cnt[gc[p]], 1u); });
+          x.par.sync();
+          const uint32_t maxc = x.par.template max<uint32_t>(G, 0u, [&](uint32_t p) { return cnt[p]; });
+          int64_t v = 0;
+          if (maxc > 1) {
+            const uint32_t maxlen = x.par.template max<uint32_t>(G, 0u, [&](uint32_t p) {
+              return cnt[p] == maxc ? (WL[p + n] - WL[p] + n - 1) : 0u;
+            });
+            v = (int64_t)maxlen * (int64_t)maxc;
+          }
+          x.par.single([&]() {
+            for (int t = 0; t < ds.n_top; ++t) if (ds.top_n[t] == (int32_t)n) r[rec_gr_fixed() + t] = v;
+          });
           x.par.sync();
         }
+        x.reset(m2);
       }
-      auto walk = [&](uint32_t t, bool wave) -> int64_t {
-        const uint32_t G = gsize((int)t);
-        if (G == 0) return 0;
-        uint32_t base = 0;
-        for (uint32_t u = 0; u < t; ++u) base += gsize((int)u);
-        uint32_t* sn = bits + t * 2 * SW;
-        const uint32_t n = (uint32_t)ds.dup_n[t];
-        return wave ? dup_walk_wave(x.par, G, n, gcall + base, sn + SW, sn, WL)
-                    : dup_walk(G, n, gcall + base, sn + SW, sn, WL);
-      };
-      if constexpr (P::kWaves > 1) {
-        // one wave per order (whole-wave walks)
-        for (uint32_t t = x.par.wave_index(); t < (uint32_t)nd; t += P::kWaves) {
-          const int64_t rep = walk(t, true);
-          if (x.par.lane == 0) r[rec_gr_fixed() + ds.n_top + t] = rep;
+      x.stamp(PH_GR_TOP);
+      if (ex) {
+        // split mode: export the word arrays; k_gr_dup_split finishes every order (top and
+        // duplicated) in its own workgroup and writes the n-gram fields
+        const uint64_t base = (x.used + 255) & ~255ull;
+        x.par.single([&]() {
+          for (int t = 0; t < ds.n_dup; ++t) r[rec_gr_fixed() + ds.n_top + t] = 0;
+          ex->wid = wid; ex->WL = WL; ex->K = K; ex->PB = PB; ex->bs = w.bs; ex->be = w.be;
+          ex->b = b_export ? b_export : b;
+          ex->free_base = x.scr + base;
+          ex->free_cap = x.cap > base ? x.cap - base : 0;
+          ex->W = W;
+          ex->valid = x.overflow ? 0u : 1u;
+        });
+        x.par.sync();
+      } else if (ds.n_dup > 0) {
+        // Two phases over all requested orders n (reference find_all_duplicate,
+        // utils/text.rs:241-259):
+        //   1. per n: canonicalise the n-gram concatenations into gc_n (exact: hash groups, then
+        //      word-id / byte equality) and mark repeated positions in R_n (p with gc[p] != p, and
+        //      their first occurrence gc[p]);
+        //   2. the greedy walks of all orders run at once, one lane each (they are independent
+        //      and sequential, so n walks cost about the longest one instead of their sum).
+        // Arrays of all orders are packed back to back: gc_n at gbase(t), bitmaps at t * 2 * SW.
+        const uint32_t SW = (W + 31) / 32 + 1;
+        const int nd = ds.n_dup;
+        auto gsize = [&](int t) -> uint32_t {
+          const uint32_t n = (uint32_t)ds.dup_n[t];
+          return (n == 0 || W < n) ? 0u : W - n + 1;
+        };
+        uint32_t gtot = 0;
+        for (int t = 0; t < nd; ++t) gtot += gsize(t);
+        const auto m3 = x.mark();
+        uint32_t* bits = x.template alloc_hot<uint32_t>(2 * (uint64_t)SW * (uint64_t)nd);  // [sn | R] per order
+        // wave documents keep the canonical ids in 16 bits (half the slice; W < kWave16)
+        using GcT = std::conditional_t<P::kWaves == 1, uint16_t, uint32_t>;
+        GcT* gcall = x.template alloc_hot_keep<GcT>((uint64_t)gtot + 1, 6ull * W + 64);
+        if (x.overflow) return;
+        x.par.for_n(2 * SW * (uint32_t)nd, [&](uint32_t i) { bits[i] = 0; });
+        x.par.sync();
+        uint32_t gb = 0;
+        for (int t = 0; t < nd; ++t) {
+          const uint32_t n = (uint32_t)ds.dup_n[t];
+          const uint32_t G = gsize(t);
+          if (G == 0) continue;
+          GcT* gc = gcall + gb;
+          uint32_t* R = bits + (uint32_t)t * 2 * SW + SW;
+          gb += G;
+          auto mark_rep = [&](uint32_t p, uint32_t g) {
+            if (g != p) {  // repeated: the position and its first occurrence
+              P::or32(&R[p >> 5], 1u << (p & 31));
+              P::or32(&R[g >> 5], 1u << (g & 31));
+            }
+          };
+          if constexpr (P::kWaves != 1) {
+            // fused into the canonicalisation's last pass
+            canonicalize_res(
+                x, G, [&](uint32_t p) { return dg.key(p, n); }, [&](uint32_t p, uint32_t q) { return dg.eq(p, q, n); },
+                gc, mark_rep);
+            x.stamp(PH_GR_DUP_CANON);
+          } else {
+            // own pass in the one-wave kernel (the fused form costs it registers)
+            canonicalize(
+                x, G, [&](uint32_t p) { return dg.key(p, n); }, [&](uint32_t p, uint32_t q) { return dg.eq(p, q, n); },
+                gc);
+            x.stamp(PH_GR_DUP_CANON);
+            x.par.for_n(G, [&](uint32_t p) { mark_rep(p, gc[p]); });
+            x.par.sync();
+          }
         }
-      } else {
-        // one lane per order: the orders' walks overlap (the whole-wave walk would run them
-        // one after another)
-        x.par.for_n((uint32_t)nd, [&](uint32_t t) { r[rec_gr_fixed() + ds.n_top + t] = walk(t, false); });
+        auto walk = [&](uint32_t t, bool wave) -> int64_t {
+          const uint32_t G = gsize((int)t);
+          if (G == 0) return 0;
+          uint32_t base = 0;
+          for (uint32_t u = 0; u < t; ++u) base += gsize((int)u);
+          uint32_t* sn = bits + t * 2 * SW;
+          const uint32_t n = (uint32_t)ds.dup_n[t];
+          return wave ? dup_walk_wave(x.par, G, n, gcall + base, sn + SW, sn, WL)
+                      : dup_walk(G, n, gcall + base, sn + SW, sn, WL);
+        };
+        if constexpr (P::kWaves > 1) {
+          // one wave per order (whole-wave walks)
+          for (uint32_t t = x.par.wave_index(); t < (uint32_t)nd; t += P::kWaves) {
+            const int64_t rep = walk(t, true);
+            if (x.par.lane == 0) r[rec_gr_fixed() + ds.n_top + t] = rep;
+          }
+        } else {
+          // one lane per order: the orders' walks overlap (the whole-wave walk would run them
+          // one after another)
+          x.par.for_n((uint32_t)nd, [&](uint32_t t) { r[rec_gr_fixed() + ds.n_top + t] = walk(t, false); });
+        }
+        x.par.sync();
+        x.stamp(PH_GR_DUP_WALK);
+        x.reset(m3);
+        x.stamp(PH_GR_DUP);
       }
-      x.par.sync();
-      x.stamp(PH_GR_DUP_WALK);
-      x.reset(m3);
-      x.stamp(PH_GR_DUP);
     }
   }
   x.reset(mark);
@@ -2965,7 +3055,9 @@ constexpr bool kHotProps = TB_HOT_PROPS != 0;
 // kPre: the document comes with its pre-pass (StageOut::pre: code points, words, runs of '\n');
 // a separate instantiation, so the common kernel carries no branch for it (a runtime branch
 // doubled the workgroup kernel's register spill).
-template <class P, bool kWithLid = true, bool kPre = false>
+// kExport: the one-wave build for launches in split mode (gopher_rep_record): no in-stage n-gram
+// code and no prefix hash, which nothing reads there.
+template <class P, bool kWithLid = true, bool kPre = false, bool kExport = false>
 TB_HD void analyze_stage(DocCtx<P>& x, const DevStage& st, const DevPlan& plan,
                          const LidTables& lid, const uint8_t* b, uint32_t n, StageOut& out) {
   bool need_words = false, need_lines = false, need_ph = false, need_lid = false;
@@ -2975,6 +3067,20 @@ TB_HD void analyze_stage(DocCtx<P>& x, const DevStage& st, const DevPlan& plan,
     if (k == DK_GOPHER_REP) need_words = need_ph = true;
     if (k == DK_FINEWEB) need_words = need_lines = need_ph = true;
     if (k == DK_LANGID) need_lid = true;
+  }
+  if constexpr (P::kWaves == 1) {
+    // One-wave documents: dup_spans (duplicated lines and paragraphs, FineWeb's duplicated lines)
+    // compares the spans themselves, so the prefix hashes have one reader left, the word hashes of
+    // a GopherRepetition step whose n-gram orders run in this kernel: not exported to the n-gram
+    // kernels, because split mode is off or the stage has two such steps.
+    int n_gr = 0;
+    bool gr_ngrams = false;
+    for (int s = 0; s < st.n_steps; ++s) {
+      if (st.steps[s].kind != DK_GOPHER_REP) continue;
+      ++n_gr;
+      gr_ngrams |= st.steps[s].n_top + st.steps[s].n_dup > 0;
+    }
+    need_ph = !kExport && gr_ngrams && !(n_gr == 1 && out.gr_export);
   }
   x.stamp(PH_START);
   if (out.line_stats) x.par.single([&]() { out.line_stats[0] = kLineStatsNone; });
@@ -3030,7 +3136,9 @@ TB_HD void analyze_stage(DocCtx<P>& x, const DevStage& st, const DevPlan& plan,
   }
   x.stamp(PH_DICT);
   PHView ph;
-  if (need_ph) ph = prefix_hash8(x, b, n);
+  if constexpr (!kExport) {
+    if (need_ph) ph = prefix_hash8(x, b, n);
+  }
   x.stamp(PH_PREFIX_HASH);
   Words w;
   if (need_words) {
@@ -3124,8 +3232,8 @@ TB_HD void analyze_stage(DocCtx<P>& x, const DevStage& st, const DevPlan& plan,
       x.stamp(PH_GQ);
     } else if (ds.kind == DK_GOPHER_REP) {
       ++gr_seen;
-      gopher_rep_record(x, ds, b, c, ph, w, r, kHotProps && gr_seen == n_gr, n_gr == 1 ? out.gr_export : nullptr,
-                        kPre ? out.pre : nullptr, out.b_global, L);
+      gopher_rep_record<P, kExport>(x, ds, b, c, ph, w, r, kHotProps && gr_seen == n_gr,
+                                    n_gr == 1 ? out.gr_export : nullptr, kPre ? out.pre : nullptr, out.b_global, L);
     } else if (ds.kind == DK_FINEWEB) {
       const auto mark = x.mark();
       uint32_t* nb = x.template alloc<uint32_t>(L.n + 1);

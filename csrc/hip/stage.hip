@@ -13,7 +13,7 @@ namespace {
 // the spills it adds sit outside the per-chunk loops) with a 5 KB LDS slice per wave: 4.55 vs
 // 5.05 ms per launch at 6 waves / 6.5 KB, 7 waves no gain (profiles/r8_wpe/; 6 beat 4 and 5 before,
 // profiles/r7_ngram/ab_occupancy.txt; before the move 4 waves won, round 2).
-#define TB_STAGE_KERNEL(NAME, ATTR)                                                                   \
+#define TB_STAGE_KERNEL(NAME, ATTR, EXPORT)                                                           \
   __global__ __launch_bounds__(64) ATTR void NAME(                                                   \
       const DevPlan* __restrict__ plan, const DevStage* __restrict__ stage, const uint8_t* __restrict__ bytes, \
       const int64_t* __restrict__ off, const int32_t* __restrict__ perm, int32_t ndocs, char* scratch,        \
@@ -30,13 +30,17 @@ namespace {
     if (line_stats) out.line_stats = line_stats + line_stats_base(off[doc], doc);                     \
     if (gr_export) { out.gr_export = gr_export + blockIdx.x; out.b_global = bytes + off[doc]; }       \
     out.dict = dict;                                                                                  \
-    analyze_stage<WavePar, false>(x, *stage, *plan, LidTables{}, b, n, out); /* LD: own kernel */ \
+    /* (language id: its own kernel) */                                                               \
+    analyze_stage<WavePar, false, false, EXPORT>(x, *stage, *plan, LidTables{}, b, n, out);           \
   }
 
 #ifndef TB_STAGE_WPE
 #define TB_STAGE_WPE 8
 #endif
-TB_STAGE_KERNEL(k_stage_analyze_wave, __attribute__((amdgpu_waves_per_eu(TB_STAGE_WPE, 8))))
+TB_STAGE_KERNEL(k_stage_analyze_wave, __attribute__((amdgpu_waves_per_eu(TB_STAGE_WPE, 8))), false)
+// launches with an export (split mode: tb_stage_analyze with gr_export): the n-gram kernels take
+// the words, so the in-stage n-gram code and the prefix hash are compiled out of this build
+TB_STAGE_KERNEL(k_stage_analyze_wave_ex, __attribute__((amdgpu_waves_per_eu(TB_STAGE_WPE, 8))), true)
 
 // Register budget of the long-document stage kernel: 6 waves per SIMD (<= 80 VGPRs), so with the
 // default 48 KB LDS slice three 512-thread workgroups (three documents) share a CU instead of one
@@ -122,7 +126,7 @@ int tb_stage_analyze(hipStream_t stream, const void* plan, const void* stage, co
   if (d->ndocs <= 0) return 0;
   const int32_t nblocks = d->n_launch <= 0 ? d->ndocs : d->n_launch;
   if (lds_bytes > kMaxLdsPerDoc) return (int)hipErrorInvalidValue;
-  auto kern = k_stage_analyze_wave;  // the one build (see TB_STAGE_KERNEL)
+  auto kern = gr_export ? k_stage_analyze_wave_ex : k_stage_analyze_wave;
   if (lds_bytes > 65536)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds_bytes, stream, (const DevPlan*)plan,

@@ -311,7 +311,9 @@ class Kernels:
         (uint32, >= 4 * (total bytes / 8 + 16 ndocs) + 16): the C4 line export (docproc.h
         StageOut::line_stats), document d at 4 * (off[d] / 8 + 16 d). ``gr_export`` (zeroed, >=
         n_launch descriptors): split mode, every launched document exports its word arrays and
-        gr_split_wave finishes its n-gram orders."""
+        gr_split_wave finishes its n-gram orders (the launcher then runs k_stage_analyze_wave_ex,
+        the build without the in-stage n-gram code: the stage must have exactly one
+        GopherRepetition step with n-gram orders, or its documents go to the CPU path)."""
         if gr_export is not None and gr_export.nbytes < max(docs.n_launch, 0) * self.sizeof_gr_export:
             raise DeviceError("stage_analyze: export buffer too small")
         rc = self.lib.tb_stage_analyze(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work, tables,
