@@ -1106,16 +1106,29 @@ TB_HD bool is_stop_word(const UcdView& ucd, const DevStopSet& ss, const Cps& cv,
   while (true) {
     const uint64_t k = ss.keys[slot];
     if (k == 0) return false;
-    if (k == key) {
-      const int32_t w = ss.idx[slot];
-      const int32_t o0 = ss.off[w], o1 = ss.off[w + 1];
-      if ((uint32_t)(o1 - o0) != len) return false;
-      int32_t pos = o0;
-      bool ok = true;
-      lower_bytes(ucd, cv, s, e, [&](uint8_t v) { ok = ok && ss.blob[pos++] == v; });
-      return ok;
-    }
+    if (k == key) break;
     slot = (slot + 1) & (kStopTableSize - 1);
+  }
+  // An entry with this key and other bytes is not the answer: another entry with the same key may
+  // follow it on the probe chain (add_stop_set puts it in the next free slot). Only the slot stays
+  // live across the comparison: the key is read back from it, the length test is the walk's end.
+  while (true) {
+    const int32_t w = ss.idx[slot];
+    const int32_t o1 = ss.off[w + 1];
+    int32_t pos = ss.off[w];
+    bool ok = true;
+    lower_bytes(ucd, cv, s, e, [&](uint8_t v) {
+      ok = ok && pos < o1 && ss.blob[pos] == v;
+      ++pos;
+    });
+    if (ok && pos == o1) return true;
+    const uint64_t same = ss.keys[slot];
+    uint64_t k;
+    do {
+      slot = (slot + 1) & (kStopTableSize - 1);
+      k = ss.keys[slot];
+      if (k == 0) return false;
+    } while (k != same);
   }
 }
 

@@ -1,6 +1,13 @@
 """Gopher repetition / quality filters and the text helpers they use (ports reference
 gopher_rep.rs and gopher_quality.rs test modules)."""
+import os
+import sys
+
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from collision_corpus import ref_all_dup as _ref_all_dup  # noqa: E402
+from collision_corpus import ref_top as _ref_top  # noqa: E402
 
 from textblaster_amd.data_model import TextDocument
 from textblaster_amd.errors import DocumentFiltered
@@ -202,32 +209,6 @@ def test_stop_words(seg):
     h.process(doc("no stop words here"))
     h.min_stop_words = None
     h.process(doc("no stop words here"))
-
-
-def _ref_top(words, n):
-    if n == 0 or len(words) < n:
-        return 0
-    cnt = {}
-    for i in range(len(words) - n + 1):
-        g = " ".join(words[i:i + n])
-        cnt[g] = cnt.get(g, 0) + 1
-    m = max(cnt.values())
-    return 0 if m <= 1 else max(len(g.encode()) * m for g, c in cnt.items() if c == m)
-
-
-def _ref_all_dup(words, n):
-    if n == 0 or len(words) < n:
-        return 0
-    seen, rep, i = set(), 0, 0
-    while i + n <= len(words):
-        g = "".join(words[i:i + n])
-        if g in seen:
-            rep += len(g.encode())
-            i += n
-        else:
-            seen.add(g)
-            i += 1
-    return rep
 
 
 def test_ngram_statistics_match_string_reference():
