@@ -12,9 +12,11 @@
 // A lane counts the words that start in its byte range, wherever they end.
 //
 // Normalisation. Cased tokenizers need none beyond the classes. With lowercase / strip_accents
-// ASCII is folded here and every other code point must carry the "normalises to itself" bit of its
-// combination; a document with one that does not is counted on the host (kBpeHost), as are
-// documents with invalid UTF-8 or the text of an added token (the library splits on those first).
+// ASCII is folded here; the identity counter (wp_*) then needs every other code point to carry the
+// "normalises to itself" bit of its combination and counts a document with one that does not on
+// the host (kBpeHost), as it does documents with invalid UTF-8 or the text of an added token (the
+// library splits on those first). The folding counter (wpf_*, below) reads what the normalizer
+// makes of such a code point from wp_fold.inc and counts those documents too.
 //
 // Pieces. The vocabulary is an open-addressed table keyed by a 64-bit hash of (continuation flag,
 // piece bytes); the piece bytes themselves sit in a pool, and every slot whose key matches is
@@ -56,6 +58,9 @@ struct DevWp {
   const uint16_t* cls1;  // wp_classes.inc two-stage table, one byte per code point
   const uint8_t* cls2;
   const uint8_t* added;  // contents of the added tokens, concatenated
+  const uint16_t* fold1;  // wp_fold.inc of the tokenizer's mode: stage 1, null = no folding beyond ASCII
+  const uint16_t* fold2;  // stage 2: 0 identity, kWpFoldHost, kWpFoldHangul, else 1 + record offset
+  const uint8_t* foldp;   // records: header (bytes | class << 4 | unclean class << 6), output bytes
   uint64_t asc0, asc1, asc2, asc3;  // classes of U+0000..7F, 2 bits each, for this cls_shift
   uint32_t mask;
   uint32_t flags;        // kWpLower | kWpChinese
@@ -275,6 +280,245 @@ TB_HD int64_t wp_count_range(const DevWp& T, const uint8_t* b, int64_t n, int64_
 TB_HD int32_t wp_count_doc(const DevWp& T, const uint8_t* b, int64_t n) {
   if (T.n_added && wp_has_added(T, b, n, 0, n)) return kBpeHost;
   const int64_t k = n > 0 ? wp_count_range(T, b, n, 0, n) : 0;
+  if (k < 0 || k + T.post_add > 0x7FFFFFFF) return kBpeHost;
+  return (int32_t)(k + T.post_add);
+}
+
+// ---- folding variant: lowercase / strip_accents beyond ASCII (wp_fold.inc) -------------------------
+// One input code point becomes 0 to 3 output code points (at most 12 bytes), read from the fold
+// table of the tokenizer's mode, or by arithmetic for a Hangul syllable. Its effective class is the
+// output's (an empty output is a drop); pieces are hashed and compared over output bytes, and a
+// search position is a pair (input byte offset of a code point, byte offset into its output), so
+// a piece may end between the jamo of one syllable. A code point whose place depends on context
+// (kWpFoldHost in the table) sends the document to the host.
+constexpr uint32_t kWpFoldHost = 0xFFFF;
+constexpr uint32_t kWpFoldHangul = 0xFFFE;
+
+struct WpOut {
+  int cls;       // effective class; -1: invalid UTF-8 or a host code point
+  int len;       // input bytes
+  int nb;        // output bytes when cls == WP_KEEP, else 0
+  uint32_t src;  // where they are: 0 the input bytes, bit 31 | Hangul syllable index, else fold pool offset
+};
+
+TB_HD int wp_u8len(uint32_t lead) { return lead < 0x80 ? 1 : (lead < 0xE0 ? 2 : (lead < 0xF0 ? 3 : 4)); }
+
+// output byte j (< c.nb) of the code point c = wpf_cp(T, b, q, n)
+TB_HD uint32_t wpf_byte(const DevWp& T, const uint8_t* b, int64_t q, const WpOut& c, int j) {
+  if (c.src == 0) return wp_byte(T, b[q + j]);
+  if (c.src & 0x80000000u) {
+    // NFD of a syllable: U+1100 + L, U+1161 + V and, if T != 0, U+11A7 + T; in UTF-8 E1 84..87 80..BF
+    const uint32_t s = c.src & 0x7FFFFFFFu;
+    const int t = j / 3, r = j - 3 * t;
+    const uint32_t cp = t == 0 ? 0x1100 + s / 588 : (t == 1 ? 0x1161 + (s % 588) / 28 : 0x11A7 + s % 28);
+    return r == 0 ? 0xE1u : (r == 1 ? 0x80 | ((cp >> 6) & 0x3F) : 0x80 | (cp & 0x3F));
+  }
+  return T.foldp[c.src + j];
+}
+
+// The code point at b[i] (i < n) as the folding normalizer leaves it.
+TB_HD WpOut wpf_cp(const DevWp& T, const uint8_t* b, int64_t i, int64_t n) {
+  WpOut r;
+  r.nb = 0;
+  r.src = 0;
+  const uint32_t c0 = b[i];
+  if (c0 < 0x80) {
+    r.len = 1;
+    const uint64_t w = c0 < 64 ? (c0 < 32 ? T.asc0 : T.asc1) : (c0 < 96 ? T.asc2 : T.asc3);
+    r.cls = (int)((w >> (2 * (c0 & 31))) & 3);
+    r.nb = r.cls == WP_KEEP;
+    return r;
+  }
+  int len;
+  const int32_t c = bpe_decode(b, i, n, &len);
+  r.len = len;
+  if (c < 0) {
+    r.cls = -1;
+    return r;
+  }
+  const uint32_t e = T.fold2[(uint32_t)T.fold1[c >> 7] * 128 + (c & 127)];
+  if (e == 0) {
+    int k = (int)((T.cls2[(uint32_t)T.cls1[c >> 7] * 128 + (c & 127)] >> T.cls_shift) & 3);
+    if (k == WP_ISO && !(T.flags & kWpChinese) && wp_is_cjk((uint32_t)c)) k = WP_KEEP;
+    r.cls = k;
+    if (k == WP_KEEP) r.nb = len;
+    return r;
+  }
+  if (e == kWpFoldHost) {
+    r.cls = -1;
+    return r;
+  }
+  if (e == kWpFoldHangul) {
+    const uint32_t s = (uint32_t)c - 0xAC00;
+    r.cls = WP_KEEP;
+    r.nb = s % 28 ? 9 : 6;
+    r.src = 0x80000000u | s;
+    return r;
+  }
+  const uint32_t h = T.foldp[e - 1];
+  int k = (int)((h >> (T.cls_shift ? 6 : 4)) & 3);
+  if (k == WP_ISO && !(T.flags & kWpChinese) && wp_is_cjk((uint32_t)c)) k = WP_KEEP;
+  r.cls = k;
+  if (k == WP_KEEP) {
+    // a kept output carries no spaces; an ideograph kept only for want of handle_chinese_chars
+    // was recorded with the two spaces around it
+    const int sp = (h & 15) > 0 && T.foldp[e] == ' ';
+    r.nb = (int)(h & 15) - 2 * sp;
+    r.src = e + sp;
+  }
+  return r;
+}
+
+TB_HD bool wpf_find(const DevWp& T, const uint8_t* b, int64_t n, int64_t pq, int pk, uint64_t h, int nb,
+                    uint32_t cont) {
+  const uint64_t key = wp_key(h, (uint32_t)nb, cont);
+  const uint32_t lo = (cont << 31) | (uint32_t)nb;
+  uint32_t s = (uint32_t)key & T.mask;
+  for (;;) {
+    const WpSlot e = T.slots[s];
+    if (e.val == kWpEmpty) return false;
+    if (e.key == key && (uint32_t)e.val == lo) {
+      const uint8_t* w = T.pool + (e.val >> 32);
+      bool same = true;
+      int m = 0;
+      for (int64_t q = pq; m < nb && q < n;) {
+        const WpOut c = wpf_cp(T, b, q, n);
+        if (c.cls < 0) return false;
+        for (int j = q == pq ? pk : 0; j < c.nb && m < nb; ++j, ++m) same = same && w[m] == wpf_byte(T, b, q, c, j);
+        q += c.len;
+      }
+      if (same && m == nb) return true;
+    }
+    s = (s + 1) & T.mask;
+  }
+}
+
+// wp_word over the folded text: ws is the first code point with a kept, non-empty output.
+TB_HD int64_t wpf_word(const DevWp& T, const uint8_t* b, int64_t n, int64_t ws, int64_t* end) {
+  int64_t we = ws, nch = 0, rem = 0;  // output characters and their bytes
+  while (we < n) {
+    const WpOut c = wpf_cp(T, b, we, n);
+    if (c.cls < 0) return -1;
+    if (c.cls >= WP_SPACE) break;
+    for (int j = 0; j < c.nb; ++j) nch += (wpf_byte(T, b, we, c, j) & 0xC0) != 0x80;
+    rem += c.nb;
+    we += c.len;
+  }
+  *end = we;
+  if (nch > T.max_chars) return 1;
+  int64_t pieces = 0, pq = ws;
+  int pk = 0;
+  uint32_t cont = 0;
+  while (rem > 0) {
+    // the longest candidate: whole output code points from (pq, pk), at most T.longest bytes;
+    // (eq, ek): the input code point its last one came from and the output offset behind it
+    uint64_t h = 0;
+    int nb = 0, ek = pk;
+    int64_t eq = pq;
+    bool full = false;
+    for (int64_t q = pq; q < we && !full;) {
+      const WpOut c = wpf_cp(T, b, q, n);
+      for (int k = q == pq ? pk : 0; k < c.nb;) {
+        const int l = wp_u8len(wpf_byte(T, b, q, c, k));
+        if (nb + l > T.longest) {
+          full = true;
+          break;
+        }
+        for (int j = 0; j < l; ++j) h = wp_push(h, wpf_byte(T, b, q, c, k + j));
+        nb += l;
+        k += l;
+        eq = q;
+        ek = k;
+      }
+      q += c.len;
+    }
+    bool hit = false;
+    while (nb > 0) {
+      if (wpf_find(T, b, n, pq, pk, h, nb, cont)) {
+        hit = true;
+        break;
+      }
+      // take the last output code point off; at the front of an input code point's output go
+      // back to the nearest one before it that has output
+      WpOut c = wpf_cp(T, b, eq, n);
+      int s = ek - 1;
+      while (s > 0 && (wpf_byte(T, b, eq, c, s) & 0xC0) == 0x80) --s;
+      for (int j = ek - 1; j >= s; --j) h = wp_pop(h, wpf_byte(T, b, eq, c, j));
+      nb -= ek - s;
+      ek = s;
+      while (nb > 0 && ek == 0) {
+        eq = wp_back(b, eq, pq);
+        c = wpf_cp(T, b, eq, n);
+        ek = c.nb;
+      }
+    }
+    if (!hit) return 1;  // no piece at the position: the whole word is the unknown token
+    ++pieces;
+    rem -= nb;
+    pq = eq;
+    pk = ek;
+    cont = 1;
+  }
+  return pieces;
+}
+
+TB_HD int64_t wpf_count_range(const DevWp& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1) {
+  int64_t p = s0;
+  if (p > 0) {
+    if ((b[p] & 0xC0) == 0x80) {  // inside a code point that starts in the range before
+      const int64_t q = wp_back(b, p + 1, 0);
+      int l;
+      if (bpe_decode(b, q, n, &l) < 0 || q + l <= p) return -1;
+      p = q + l;
+    }
+    // a word that runs into p started before it: find the nearest code point that is no drop
+    bool inword = false;
+    for (int64_t e = p; e > 0;) {
+      const int64_t q = wp_back(b, e, 0);
+      const WpOut c = wpf_cp(T, b, q, n);
+      if (c.cls < 0 || q + c.len != e) return -1;
+      if (c.cls != WP_DROP) {
+        inword = c.cls == WP_KEEP;
+        break;
+      }
+      e = q;
+    }
+    while (inword && p < n) {
+      const WpOut c = wpf_cp(T, b, p, n);
+      if (c.cls < 0) return -1;
+      if (c.cls >= WP_SPACE) break;
+      p += c.len;
+    }
+  }
+  int64_t total = 0;
+  while (p < n && p < s1) {
+    const WpOut c = wpf_cp(T, b, p, n);
+    if (c.cls < 0) return -1;
+    if (c.cls == WP_KEEP) {
+      int64_t e;
+      const int64_t w = wpf_word(T, b, n, p, &e);
+      if (w < 0) return -1;
+      total += w;
+      p = e;
+    } else {
+      total += c.cls == WP_ISO;
+      p += c.len;
+    }
+  }
+  return total;
+}
+
+// The counter by policy: Fold = false is the identity path above, unchanged.
+template <bool Fold>
+TB_HD int64_t wp_count_range_t(const DevWp& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1) {
+  if (Fold) return wpf_count_range(T, b, n, s0, s1);
+  return wp_count_range(T, b, n, s0, s1);
+}
+
+template <bool Fold>
+TB_HD int32_t wp_count_doc_t(const DevWp& T, const uint8_t* b, int64_t n) {
+  if (T.n_added && wp_has_added(T, b, n, 0, n)) return kBpeHost;
+  const int64_t k = n > 0 ? wp_count_range_t<Fold>(T, b, n, 0, n) : 0;
   if (k < 0 || k + T.post_add > 0x7FFFFFFF) return kBpeHost;
   return (int32_t)(k + T.post_add);
 }

@@ -56,6 +56,44 @@ __global__ __launch_bounds__(kWpLanes) void k_wp_count(DevWp T, const uint8_t* _
   }
 }
 
+// k_wp_count for tokenizers with lowercase / strip_accents: the same launch shape and lane split
+// over the folding counter (wpf_count_range: classes, hashes and search positions over the
+// normalizer's output, read from the fold tables through the cache). A kernel of its own name, so
+// that its registers are budgeted apart from k_wp_count's.
+__global__ __launch_bounds__(kWpLanes) void k_wp_count_fold(DevWp T, const uint8_t* __restrict__ text,
+                                                            const int64_t* __restrict__ off,
+                                                            const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                            int32_t* __restrict__ counts) {
+  const int t = threadIdx.x;
+  int64_t n = n_max;
+  if (n_dev != nullptr) n = min(n, *n_dev);
+  for (int64_t k = blockIdx.x; k < n; k += gridDim.x) {
+    const int64_t s = off[k];
+    const int64_t len = off[k + 1] - s;
+    const uint8_t* b = text + s;
+    const int64_t chunk = max((int64_t)kWpMinChunk, (len + kWpLanes - 1) / kWpLanes);
+    const int64_t s0 = (int64_t)t * chunk;
+    long long cnt = 0;
+    int bad = 0;
+    if (s0 < len) {
+      const int64_t s1 = min(len, s0 + chunk);
+      if (T.n_added && wp_has_added(T, b, len, s0, s1)) {
+        bad = 1;
+      } else {
+        const int64_t x = wp_count_range_t<true>(T, b, len, s0, s1);
+        if (x < 0) bad = 1;
+        else cnt = x;
+      }
+    }
+    const bool any_bad = __ballot(bad) != 0;
+    for (int o = kWpLanes / 2; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, kWpLanes);
+    if (t == 0) {
+      const long long tot = cnt + T.post_add;
+      counts[k] = (any_bad || tot > 0x7FFFFFFF) ? kBpeHost : (int32_t)tot;
+    }
+  }
+}
+
 }  // namespace
 
 // counts[k] for documents k < min(*n_dev, n_max) (n_dev may be null): text + off[k] .. off[k + 1]
@@ -64,8 +102,12 @@ extern "C" int tb_wp_count(hipStream_t stream, const DevWp* T, const uint8_t* te
   if (n_max <= 0) return 0;
   if (T == nullptr || T->n_added < 0 || T->n_added > kBpeMaxAdded || T->longest < 1 || T->max_chars < 0)
     return (int)hipErrorInvalidValue;
+  if (T->fold1 != nullptr && (T->fold2 == nullptr || T->foldp == nullptr)) return (int)hipErrorInvalidValue;
   const int grid = n_max < kWpGrid ? n_max : kWpGrid;
-  hipLaunchKernelGGL(k_wp_count, dim3(grid), dim3(kWpLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+  if (T->fold1 != nullptr)
+    hipLaunchKernelGGL(k_wp_count_fold, dim3(grid), dim3(kWpLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+  else
+    hipLaunchKernelGGL(k_wp_count, dim3(grid), dim3(kWpLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
   return (int)hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include "../common/bpe_classes.inc"
 #include "../common/wordpiece.h"
 #include "../common/wp_classes.inc"
+#include "../common/wp_fold.inc"
 #include "../common/langid.h"
 #include "../common/ucd_tables.inc"
 #include "filters.h"
@@ -493,6 +494,15 @@ PYBIND11_MODULE(_tbhost, m) {
     wp_ascii_classes(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE2, shift, a.data());
     return to_numpy(std::move(a));
   });
+  m.def("wp_fold_tables", []() {
+    // wp_fold.inc for upload: stage 1 of the three modes (lowercase, strip_accents, both), the
+    // shared stage 2 and the record pool
+    std::vector<uint16_t> f1(TB_WP_FOLD_STAGE1, TB_WP_FOLD_STAGE1 + sizeof(TB_WP_FOLD_STAGE1) / 2);
+    std::vector<uint16_t> f2(TB_WP_FOLD_STAGE2, TB_WP_FOLD_STAGE2 + sizeof(TB_WP_FOLD_STAGE2) / 2);
+    std::vector<uint8_t> fp(TB_WP_FOLD_POOL, TB_WP_FOLD_POOL + sizeof(TB_WP_FOLD_POOL));
+    return py::make_tuple(to_numpy(std::move(f1)).attr("reshape")(3, TB_WP_FOLD_NSTAGE1), to_numpy(std::move(f2)),
+                          to_numpy(std::move(fp)));
+  });
   m.def("wp_build_table", [](py::array_t<uint8_t, py::array::c_style> pool, py::array_t<int64_t, py::array::c_style> off,
                              py::array_t<uint8_t, py::array::c_style> cont) {
     // pieces i = (cont[i], pool[off[i]:off[i + 1]]), distinct; open addressing, load <= 1/2.
@@ -518,13 +528,14 @@ PYBIND11_MODULE(_tbhost, m) {
                        py::array_t<uint8_t, py::array::c_style> pool, uint32_t flags, uint32_t cls_shift,
                        uint32_t self_bit, int32_t max_chars, int32_t longest,
                        py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
-                       int nthreads, int64_t chunk) {
-    // host emulation of k_wp_count: per document the token count, or kBpeHost. chunk > 0: the
-    // wave split - the words starting in each chunk-byte range counted independently
-    // (wp_count_range), as the kernel's lanes do
+                       int nthreads, int64_t chunk, int fold) {
+    // host emulation of k_wp_count (fold 0) / k_wp_count_fold (fold 1 lowercase, 2 strip_accents,
+    // 3 both: wp_fold.inc): per document the token count, or kBpeHost. chunk > 0: the wave split -
+    // the words starting in each chunk-byte range counted independently (wp_count_range), as the
+    // kernel's lanes do
     if ((size_t)slots.size() != 2 * ((size_t)mask + 1) || added_off.size() > kBpeMaxAdded + 1 ||
         (added_off.size() && added_off.back() > added.size()) || (cls_shift != 0 && cls_shift != 2) || longest < 1 ||
-        max_chars < 0)
+        max_chars < 0 || fold < 0 || fold > 3)
       throw std::invalid_argument("wp_count: operand shapes");
     static_assert(sizeof(WpSlot) == 16, "WpSlot is two uint64");
     const int64_t nd = off.size() - 1;
@@ -535,6 +546,11 @@ PYBIND11_MODULE(_tbhost, m) {
     T.cls1 = TB_WP_CLS_STAGE1;
     T.cls2 = TB_WP_CLS_STAGE2;
     T.added = added.data();
+    if (fold) {
+      T.fold1 = TB_WP_FOLD_STAGE1 + (size_t)(fold - 1) * TB_WP_FOLD_NSTAGE1;
+      T.fold2 = TB_WP_FOLD_STAGE2;
+      T.foldp = TB_WP_FOLD_POOL;
+    }
     uint64_t asc[4];
     wp_ascii_classes(T.cls1, T.cls2, cls_shift, asc);
     T.asc0 = asc[0]; T.asc1 = asc[1]; T.asc2 = asc[2]; T.asc3 = asc[3];
@@ -559,13 +575,14 @@ PYBIND11_MODULE(_tbhost, m) {
             const uint8_t* b = d + o[k];
             const int64_t n = o[k + 1] - o[k];
             if (chunk <= 0) {
-              out[k] = wp_count_doc(T, b, n);
+              out[k] = fold ? wp_count_doc_t<true>(T, b, n) : wp_count_doc(T, b, n);
               continue;
             }
             int64_t tot = T.post_add;
             bool bad = T.n_added && wp_has_added(T, b, n, 0, n);
             for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
-              const int64_t x = wp_count_range(T, b, n, s0, std::min(n, s0 + chunk));
+              const int64_t s1 = std::min(n, s0 + chunk);
+              const int64_t x = fold ? wpf_count_range(T, b, n, s0, s1) : wp_count_range(T, b, n, s0, s1);
               if (x < 0) bad = true;
               tot += x;
             }
@@ -577,7 +594,7 @@ PYBIND11_MODULE(_tbhost, m) {
     return to_numpy(std::move(out));
   }, py::arg("data"), py::arg("off"), py::arg("slots"), py::arg("mask"), py::arg("pool"), py::arg("flags"),
         py::arg("cls_shift"), py::arg("self_bit"), py::arg("max_chars"), py::arg("longest"), py::arg("added"),
-        py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0);
+        py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0, py::arg("fold") = 0);
   m.def("fmt_f64", [](double x) { return fmt_f64(x); });
   m.def("fmt_fixed", [](double x, int prec) { return fmt_fixed(x, prec); });
   m.def("contains_byte", [](py::array_t<uint8_t, py::array::c_style> a, int v) {

@@ -17,7 +17,9 @@ Split(regex) + ByteLevel(use_regex=false) with the Llama-3 / cl100k_base pattern
 (csrc/common/bpe_split.h, k_bpe_split_count): their spec also carries the vocabulary's raw bytes
 for ``ignore_merges`` and up to 1024 added tokens. WordPiece tokenizers (BertNormalizer +
 BertPreTokenizer, the BERT family) get a :class:`WordPieceSpec` instead (:meth:`TokenCounterModel.wordpiece_spec`): the vocabulary as an
-open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count).
+open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count). With ``lowercase``
+or ``strip_accents`` the device path counts with :meth:`TokenCounterModel.wordpiece_fold_spec`, which
+names the fold tables of the tokenizer's mode (csrc/common/wp_fold.inc, k_wp_count_fold).
 """
 from __future__ import annotations
 
@@ -241,16 +243,22 @@ class WordPieceSpec:
     added: np.ndarray      # uint8: added-token contents, concatenated
     added_off: List[int]   # [n_added + 1]
     post_add: int          # tokens the post-processor adds
+    fold: int = 0          # fold tables of wp_fold.inc: 0 none, 1 lowercase, 2 strip_accents, 3 both
 
 
 WP_LOWER, WP_CHINESE = 1, 2  # csrc/common/wordpiece.h kWpLower, kWpChinese
 
 
-def build_wordpiece_spec(tj: dict) -> Optional[WordPieceSpec]:
+def build_wordpiece_spec(tj: dict, fold: bool = False) -> Optional[WordPieceSpec]:
     """WordPieceSpec of a parsed tokenizer.json, or None when the tokenizer is not a WordPiece model
     behind BertNormalizer + BertPreTokenizer that the device counter reproduces exactly (no
     truncation / padding, the unknown token in the vocabulary, a known post-processor, at most
-    MAX_ADDED added tokens, none of them matched on normalised text)."""
+    MAX_ADDED added tokens, none of them matched on normalised text).
+
+    The identity spec (``fold`` false) leaves every document with a non-ASCII code point that
+    ``lowercase`` / ``strip_accents`` change to the host. With ``fold`` the spec of a tokenizer that
+    has either on names its mode's fold tables instead (k_wp_count_fold), and only the documents
+    with a code point NFD may move go to the host; a cased tokenizer's spec is the same either way."""
     from .. import native
 
     m = tj.get("model") or {}
@@ -293,11 +301,13 @@ def build_wordpiece_spec(tj: dict) -> Optional[WordPieceSpec]:
     aoff = [0]
     for t in added:
         aoff.append(aoff[-1] + len(t))
+    mode = (1 if lower else 0) | (2 if strip else 0) if fold else 0
     return WordPieceSpec(slots, int(mask), pool, (WP_LOWER if lower else 0) | (WP_CHINESE if nz.get(
         "handle_chinese_chars", True) else 0), 0 if nz.get("clean_text", True) else 2,
-        {(False, False): 0, (True, False): 1 << 4, (False, True): 1 << 5, (True, True): 1 << 6}[(lower, strip)],
+        0 if mode else {(False, False): 0, (True, False): 1 << 4, (False, True): 1 << 5,
+                        (True, True): 1 << 6}[(lower, strip)],
         max_chars, int(longest), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
-        aoff if added else [], post)
+        aoff if added else [], post, mode)
 
 
 class TokenCounterModel:
@@ -308,6 +318,7 @@ class TokenCounterModel:
         self.tok = Tokenizer.from_file(path)
         self._spec = False
         self._wp_spec = False
+        self._wp_fold_spec = False
 
     def count(self, texts: List[str]) -> List[int]:
         if not texts:
@@ -329,15 +340,28 @@ class TokenCounterModel:
                 self._wp_spec = build_wordpiece_spec(json.load(f))
         return self._wp_spec
 
+    def wordpiece_fold_spec(self) -> Optional[WordPieceSpec]:
+        """:meth:`wordpiece_spec` with the fold tables of the tokenizer's ``lowercase`` /
+        ``strip_accents`` mode (the same spec for a cased tokenizer); built once."""
+        if self._wp_fold_spec is False:
+            ident = self.wordpiece_spec()
+            if ident is None or ident.self_bit == 0:
+                self._wp_fold_spec = ident
+            else:
+                with open(self.path, encoding="utf-8") as f:
+                    self._wp_fold_spec = build_wordpiece_spec(json.load(f), fold=True)
+        return self._wp_fold_spec
+
     def device_spec(self):
-        """The spec the device path counts with: :class:`BpeSpec`, :class:`WordPieceSpec` or None."""
-        return self.bpe_spec() or self.wordpiece_spec()
+        """The spec the device path counts with: :class:`BpeSpec`, :class:`WordPieceSpec` (folding
+        when the tokenizer lowercases or strips accents) or None."""
+        return self.bpe_spec() or self.wordpiece_fold_spec()
 
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
         """Token counts of packed UTF-8 documents with the native counter of whichever spec the
         tokenizer has (host emulation of k_bpe_count / k_wp_count); documents it returns -2 for
-        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, WordPiece text the
-        normalizer would change beyond ASCII case) are counted by ``tokenizers``."""
+        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, WordPiece text with a code
+        point whose place NFD may change under strip_accents) are counted by ``tokenizers``."""
         from .. import native
 
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -360,7 +384,7 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
     h = native.host()
     if isinstance(sp, WordPieceSpec):
         return h.wp_count(data, off, sp.slots, sp.mask, sp.pool, sp.flags, sp.cls_shift, sp.self_bit, sp.max_chars,
-                          sp.longest, sp.added, sp.added_off, sp.post_add, nthreads, chunk)
+                          sp.longest, sp.added, sp.added_off, sp.post_add, nthreads, chunk, sp.fold)
     if sp.kind == BPE_GPT2:
         return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
                            nthreads, chunk)
@@ -371,7 +395,7 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
 
 
 def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
-                              lowercase: bool = False) -> str:
+                              lowercase: bool = False, strip_accents: Optional[bool] = None) -> str:
     """Train a BERT-format WordPiece tokenizer (BertNormalizer, BertPreTokenizer, ``[CLS] $A [SEP]``
     template, the five BERT special tokens, ``vocab_size`` entries) on the synthetic Zipf corpus
     and save it as ``path`` (kept if it already exists): the stand-in for bert-base-cased /
@@ -384,7 +408,7 @@ def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 
 
     texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
     tok = Tokenizer(models.WordPiece(unk_token="[UNK]"))
-    tok.normalizer = normalizers.BertNormalizer(clean_text=True, handle_chinese_chars=True, strip_accents=None,
+    tok.normalizer = normalizers.BertNormalizer(clean_text=True, handle_chinese_chars=True, strip_accents=strip_accents,
                                                 lowercase=lowercase)
     tok.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
     tok.decoder = decoders.WordPiece(prefix="##")

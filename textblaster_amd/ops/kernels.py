@@ -206,6 +206,7 @@ class BpeTables:
 class DevWp(ctypes.Structure):
     """csrc/common/wordpiece.h DevWp (checked against tb_sizeof_wp)."""
     _fields_ = [("slots", _P), ("pool", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
+                ("fold1", _P), ("fold2", _P), ("foldp", _P),
                 ("asc", ctypes.c_uint64 * 4), ("mask", _U32), ("flags", _U32), ("cls_shift", _U32),
                 ("self_bit", _U32), ("max_chars", _I32), ("longest", _I32), ("post_add", _I32), ("n_added", _I32),
                 ("added_off", _I32 * 9)]
@@ -215,7 +216,7 @@ class WpTables:
     """A WordPiece tokenizer's tables in HBM (models/tokenizer.py WordPieceSpec) and the kernel's
     parameter block pointing at them."""
 
-    def __init__(self, spec, cls_tables, ascii_classes):
+    def __init__(self, spec, cls_tables, ascii_classes, fold_tables=None):
         from . import hiprt
 
         if len(spec.added_off) > 9:
@@ -225,6 +226,15 @@ class WpTables:
         self.arrays = [hiprt.to_device(a) for a in (spec.slots, spec.pool, cls_tables[0], cls_tables[1], spec.added)]
         st = DevWp()
         st.slots, st.pool, st.cls1, st.cls2, st.added = [a.data_ptr() for a in self.arrays]
+        if spec.fold:
+            # wp_fold.inc: the stage 1 of the tokenizer's mode, the shared stage 2 and the records
+            # (tb_wp_count then launches k_wp_count_fold)
+            if fold_tables is None or not 1 <= spec.fold <= 3:
+                raise DeviceError("wordpiece: fold tables")
+            f1, f2, fp = fold_tables
+            self.arrays += [hiprt.to_device(np.ascontiguousarray(f1[spec.fold - 1])), hiprt.to_device(f2),
+                            hiprt.to_device(fp)]
+            st.fold1, st.fold2, st.foldp = [a.data_ptr() for a in self.arrays[-3:]]
         for i in range(4):
             st.asc[i] = int(ascii_classes[i])
         st.mask, st.flags, st.cls_shift, st.self_bit = spec.mask, spec.flags, spec.cls_shift, spec.self_bit
@@ -496,7 +506,7 @@ class Kernels:
         if self.lib.tb_sizeof_wp() != ctypes.sizeof(DevWp):
             raise DeviceError("libtbhip.so DevWp layout differs from the binding; rebuild")
         h = native.host()
-        return WpTables(spec, h.wp_classes(), h.wp_ascii(spec.cls_shift))
+        return WpTables(spec, h.wp_classes(), h.wp_ascii(spec.cls_shift), h.wp_fold_tables() if spec.fold else None)
 
     def wp_count(self, tabs: WpTables, text, off, n_dev, n_max: int, counts):
         """k_wp_count: WordPiece token counts under bpe_count's contract (csrc/hip/wordpiece.hip)."""

@@ -676,9 +676,9 @@ class Engine:
             rec = np.full(ndocs, -1, dtype=np.int64)
             if len(alive) and resolved is not None and resolved.n_kept_final() == len(alive):
                 # K16 agreed: final kept output k is alive[k]; its count came from k_bpe_count /
-                # k_bpe_split_count / k_wp_count (or -2: added-token text, a BPE pre-token over 2048
-                # bytes, WordPiece text the normalizer changes beyond ASCII case -> the tokenizer, like
-                # unsupported tokenizers)
+                # k_bpe_split_count / k_wp_count / k_wp_count_fold (or -2: added-token text, a BPE
+                # pre-token over 2048 bytes, accent-stripped WordPiece text with a code point NFD may
+                # reorder -> the tokenizer, like unsupported tokenizers)
                 dev = resolved.kept_tokens(i)
                 cnt = dev.astype(np.int64) if dev is not None else np.full(len(alive), -2, np.int64)
                 bad = np.nonzero(cnt < 0)[0]

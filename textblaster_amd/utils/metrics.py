@@ -87,10 +87,12 @@ DEVICE_META_FALLBACK_TOTAL = Counter("tb_device_meta_fallback_total",
                                      "fallback.", registry=REGISTRY)
 BPE_HOST_DOCS_TOTAL = Counter("tb_bpe_host_docs_total",
                               "Kept documents whose TokenCounter count the device handed to the host tokenizer "
-                              "(added-token text, a BPE pre-token over 2048 bytes, WordPiece text its normalizer "
-                              "changes beyond ASCII case, or a tokenizer with no device counter).", registry=REGISTRY)
+                              "(added-token text, invalid UTF-8, a BPE pre-token over 2048 bytes, accent-stripped "
+                              "WordPiece text with a code point NFD may reorder, or a tokenizer with no device "
+                              "counter).", registry=REGISTRY)
 BPE_DEVICE_DOCS_TOTAL = Counter("tb_bpe_device_docs_total",
-                                "Kept documents whose TokenCounter count came from k_bpe_count / k_wp_count.",
+                                "Kept documents whose TokenCounter count came from a device kernel (k_bpe_count, "
+                                "k_bpe_split_count, k_wp_count, k_wp_count_fold).",
                                 registry=REGISTRY)
 RANK = Gauge("tb_rank", "Data-parallel rank of this process.", registry=REGISTRY)
 WORLD_SIZE = Gauge("tb_world_size", "Number of data-parallel ranks.", registry=REGISTRY)
