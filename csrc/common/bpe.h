@@ -28,9 +28,15 @@
 // it contains the text of an added token (HF splits on those before pre-tokenizing), holds invalid
 // UTF-8, or has a pre-token longer than kBpeMaxLong bytes.
 //
+// NFC. A tokenizer whose normalizer is NFC (the Qwen2 family) is counted on documents that the
+// normaliser provably leaves unchanged, and the device does not normalise: bpe_nfc_range runs the
+// Unicode quick check over the code points as they are decoded (nfc_qc.inc, generated from the
+// library's own NFC by tools/gen_nfc_qc.py), and every other document goes to the host.
+//
 // The counting loops (bpe_count_span / _range / _doc) take the pre-tokenizer as a policy: BpeGpt2
 // below is the regex above; BpeSplit (bpe_split.h) is the Split(regex) + ByteLevel(use_regex=false)
-// layout of Llama-3, cl100k_base and Qwen2, with ignore_merges and added tokens kept in memory.
+// layout of Llama-3, cl100k_base and Qwen2, with ignore_merges and added tokens kept in memory;
+// BpeCase (bpe_case.h) is the same layout with the case-aware pattern of o200k_base or Tekken.
 #pragma once
 #include "tb_common.h"
 
@@ -46,8 +52,11 @@ constexpr int32_t kBpeHost = -2;  // count it on the host
 constexpr int32_t kBpeLong = -3;
 constexpr int kBpeMaxLong = 2048;  // longest pre-token merged on the device
 
-// the pre-tokenizer: GPT-2's ByteLevel regex, or Split(pattern A / B) + ByteLevel(use_regex=false)
-enum BpeKind : int { kBpeGpt2 = 0, kBpeSplitA = 1, kBpeSplitB = 2 };
+// the pre-tokenizer: GPT-2's ByteLevel regex, or Split(pattern) + ByteLevel(use_regex=false) with
+// pattern A / B (bpe_split.h) or the case-aware C / D (bpe_case.h)
+enum BpeKind : int { kBpeGpt2 = 0, kBpeSplitA = 1, kBpeSplitB = 2, kBpeCaseC = 3, kBpeCaseD = 4 };
+TB_HD bool bpe_kind_case(int kind) { return kind == kBpeCaseC || kind == kBpeCaseD; }
+TB_HD bool bpe_kind_split(int kind) { return kind == kBpeSplitA || kind == kBpeSplitB || bpe_kind_case(kind); }
 constexpr int kBpeSplitMaxAdded = 1024;
 constexpr int kBpeSplitMaxAddedBytes = 65536;
 
@@ -69,11 +78,17 @@ struct DevBpe {
   const int32_t* aoff;       // [n_added + 1]: offsets into added
   const uint64_t* vslots;    // [2 * (vmask + 1)]: WpSlot pairs (wordpiece.h) over the entries' raw bytes
   const uint8_t* vpool;      // the entries' raw bytes
+  const uint8_t* nfc1;       // nfc_qc.inc two-stage table (nfc != 0 only)
+  const uint8_t* nfc2;
+  const uint16_t* ccls1;     // bpe_case_classes.inc two-stage class table (kBpeCaseC / D only)
+  const uint32_t* ccls2;
   uint64_t amask[4];         // bit x: an added token starts with byte x
   uint32_t vmask;
   int32_t vlongest;          // bytes of the longest vocabulary entry
-  int32_t kind;              // kBpeGpt2 / kBpeSplitA / kBpeSplitB
+  int32_t kind;              // BpeKind
   int32_t ignore_merges;     // a pre-token that is a vocabulary entry is one token
+  int32_t nfc;               // the normalizer is NFC: count only the documents it leaves unchanged
+  int32_t pad_;
 };
 
 TB_HD uint64_t bpe_hash(uint64_t k) {
@@ -285,6 +300,47 @@ TB_HD int64_t bpe_prev_start(const uint8_t* b, int64_t i) {
   return p;
 }
 
+// ---- the NFC gate ----
+// nfc_qc.inc: the canonical combining class of a code point, or kBpeNfcNotYes when it is not
+// NFC_QC=Yes (it changes under NFC, or may compose with what precedes it); below U+0300 every code
+// point is a starter that NFC keeps.
+constexpr int kBpeNfcNotYes = 255;
+constexpr uint32_t kBpeNfcFirst = 0x300;
+
+TB_HD int bpe_nfc_entry(const DevBpe& T, uint32_t c) {
+  return c < kBpeNfcFirst ? 0 : (int)T.nfc2[(uint32_t)T.nfc1[c >> 7] * 128 + (c & 127)];
+}
+
+// The quick check over the code points that start in [s0, s1): 1 when none of them is not-Yes and
+// none with a non-zero class follows a code point of a higher class (the one before the range
+// included, so the ranges of a partition decide together whether NFC is the identity on the
+// document); 0 otherwise; -1 on invalid UTF-8.
+TB_HD int bpe_nfc_range(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0, int64_t s1) {
+  int64_t i = s0;
+  while (i < s1 && (b[i] & 0xC0) == 0x80) ++i;
+  int prev = 0, l;
+  if (i > 0 && i < s1) {
+    const int64_t p = bpe_prev_start(b, i);
+    const int32_t c = bpe_decode(b, p, n, &l);
+    if (c < 0 || p + l != i) return -1;
+    prev = bpe_nfc_entry(T, (uint32_t)c);
+  }
+  while (i < s1) {
+    if (b[i] < 0x80) {
+      prev = 0;
+      ++i;
+      continue;
+    }
+    const int32_t c = bpe_decode(b, i, n, &l);
+    if (c < 0) return -1;
+    const int e = bpe_nfc_entry(T, (uint32_t)c);
+    if (e == kBpeNfcNotYes || (e && prev > e)) return 0;
+    prev = e;
+    i += l;
+  }
+  return 1;
+}
+
 // R1 || R2 at the code point start i (0 < i < n): 1 / 0, -1 on invalid UTF-8
 TB_HD int bpe_b12(const DevBpe& T, const uint8_t* b, int64_t n, int64_t i) {
   int l1, l0;
@@ -409,6 +465,7 @@ template <class P = BpeGpt2, class LongF = BpeNoLong>
 TB_HD int32_t bpe_count_doc(const DevBpe& T, const uint8_t* b, int64_t n, BpeArr c, BpeArr r,
                             LongF&& on_long = LongF{}) {
   if (T.n_added && P::has_added(T, b, n, 0, n)) return kBpeHost;
+  if (T.nfc && bpe_nfc_range(T, b, n, 0, n) != 1) return kBpeHost;
   const int64_t k = bpe_count_span<true, P>(T, b, n, 0, n, c, r, on_long);
   if (k < 0 || k + T.post_add > 0x7FFFFFFF) return kBpeHost;
   return (int32_t)(k + T.post_add);

@@ -1,6 +1,7 @@
 // Byte-level BPE token counting for tokenizers whose pre-tokenizer is
 // Sequence[Split(Regex(P), Isolated), ByteLevel(use_regex=false)] (Llama-3, the cl100k_base
-// conversions, Qwen2 without its normalizer): the policy BpeSplit of the counting loops of bpe.h.
+// conversions, Qwen2; behind Qwen2's NFC normalizer the NFC gate of bpe.h decides per document): the
+// policy BpeSplit of the counting loops of bpe.h.
 // Shared by the HIP kernels (csrc/hip/bpe.hip k_bpe_split_count / k_bpe_split_long) and the host
 // emulation (csrc/host/module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
 //

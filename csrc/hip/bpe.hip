@@ -15,10 +15,15 @@
 // Both kernels are written once over the pre-tokenizer policy (csrc/common/bpe.h): k_bpe_count /
 // k_bpe_long are the GPT-2 instantiation, k_bpe_split_count / k_bpe_split_long the split-regex
 // one (csrc/common/bpe_split.h: Llama-3, cl100k_base, Qwen2), whose lanes start at their range's
-// first sync point and stop at the next lane's.
+// first sync point and stop at the next lane's. k_bpe_split_count_nfc is k_bpe_split_count for a
+// tokenizer whose normalizer is NFC: each lane also runs the quick check (bpe_nfc_range) over the
+// code points of its byte range, and a document that fails it goes to the host; the check is a
+// compile-time parameter of the body, so the other kernels carry none of it. k_bpe_case_count /
+// k_bpe_case_count_nfc / k_bpe_case_long are the instantiation for the case-aware patterns of
+// o200k_base and Tekken (csrc/common/bpe_case.h).
 #include <hip/hip_runtime.h>
 
-#include "../common/bpe_split.h"
+#include "../common/bpe_case.h"
 
 using namespace tb;
 
@@ -61,7 +66,7 @@ __device__ __forceinline__ int64_t lane_count(const DevBpe& T, const uint8_t* b,
   return bpe_count_span<kMerge, P>(T, b, len, lo, hi, c, r, on_long);
 }
 
-template <class P>
+template <class P, bool kNfc = false>
 __device__ __forceinline__ void bpe_count_body(const DevBpe& T, const uint8_t* __restrict__ text,
                                                const int64_t* __restrict__ off, const int64_t* __restrict__ n_dev,
                                                int32_t n_max, int32_t* __restrict__ counts) {
@@ -83,6 +88,8 @@ __device__ __forceinline__ void bpe_count_body(const DevBpe& T, const uint8_t* _
     lane_span<P>(T, b, len, s0, s1, t, &lo, &hi);
     if (s0 < len) {
       if (T.n_added && P::has_added(T, b, len, s0, s1)) {
+        bad = 1;
+      } else if (kNfc && bpe_nfc_range(T, b, len, s0, s1) != 1) {
         bad = 1;
       } else {
         const int64_t x = lane_count<true, P>(T, b, len, lo, hi, BpeArr{cs + t, kBpeLanes}, BpeArr{rs + t, kBpeLanes},
@@ -117,6 +124,29 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_split_count(DevBpe T, const u
                                                                const int64_t* __restrict__ n_dev, int32_t n_max,
                                                                int32_t* __restrict__ counts) {
   bpe_count_body<BpeSplit>(T, text, off, n_dev, n_max, counts);
+}
+
+// k_bpe_split_count behind the NFC gate (T.nfc)
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_split_count_nfc(DevBpe T, const uint8_t* __restrict__ text,
+                                                                   const int64_t* __restrict__ off,
+                                                                   const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                                   int32_t* __restrict__ counts) {
+  bpe_count_body<BpeSplit, true>(T, text, off, n_dev, n_max, counts);
+}
+
+// k_bpe_count for the case-aware split patterns (C and D, T.kind), and behind the NFC gate
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_case_count(DevBpe T, const uint8_t* __restrict__ text,
+                                                              const int64_t* __restrict__ off,
+                                                              const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                              int32_t* __restrict__ counts) {
+  bpe_count_body<BpeCase>(T, text, off, n_dev, n_max, counts);
+}
+
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_case_count_nfc(DevBpe T, const uint8_t* __restrict__ text,
+                                                                  const int64_t* __restrict__ off,
+                                                                  const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                                  int32_t* __restrict__ counts) {
+  bpe_count_body<BpeCase, true>(T, text, off, n_dev, n_max, counts);
 }
 
 constexpr int kBpeLongList = 32;  // long pre-tokens of one document counted on the device
@@ -238,6 +268,14 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_split_long(DevBpe T, const ui
   bpe_long_body<BpeSplit>(T, text, off, n_dev, n_max, counts);
 }
 
+// k_bpe_long for the case-aware split patterns
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_case_long(DevBpe T, const uint8_t* __restrict__ text,
+                                                             const int64_t* __restrict__ off,
+                                                             const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                             int32_t* __restrict__ counts) {
+  bpe_long_body<BpeCase>(T, text, off, n_dev, n_max, counts);
+}
+
 }  // namespace
 
 // counts[k] for documents k < min(*n_dev, n_max) (n_dev may be null): text + off[k] .. off[k + 1]
@@ -245,16 +283,30 @@ extern "C" int tb_bpe_count(hipStream_t stream, const DevBpe* T, const uint8_t* 
                             const int64_t* n_dev, int32_t n_max, int32_t* counts) {
   if (n_max <= 0) return 0;
   if (T == nullptr || T->n_added < 0) return (int)hipErrorInvalidValue;
-  const bool split = T->kind == kBpeSplitA || T->kind == kBpeSplitB;
+  const bool split = bpe_kind_split(T->kind), cased = bpe_kind_case(T->kind);
   if (split ? (T->n_added > kBpeSplitMaxAdded || (T->n_added && (T->aoff == nullptr || T->added == nullptr)) ||
                (T->ignore_merges && (T->vslots == nullptr || T->vpool == nullptr || T->vlongest < 1)))
             : (T->kind != kBpeGpt2 || T->n_added > kBpeMaxAdded))
     return (int)hipErrorInvalidValue;
+  if (T->nfc && (!split || T->nfc1 == nullptr || T->nfc2 == nullptr)) return (int)hipErrorInvalidValue;
+  if (cased && (T->ccls1 == nullptr || T->ccls2 == nullptr)) return (int)hipErrorInvalidValue;
   const int grid = n_max < kBpeGrid ? n_max : kBpeGrid;
   // the documents with pre-tokens over kBpeMaxWord bytes (grid-stride; the others are skipped)
   const int grid_long = n_max < kBpeGrid / 4 ? n_max : kBpeGrid / 4;
-  if (split) {
-    hipLaunchKernelGGL(k_bpe_split_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+  if (cased) {
+    if (T->nfc)
+      hipLaunchKernelGGL(k_bpe_case_count_nfc, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
+                         counts);
+    else
+      hipLaunchKernelGGL(k_bpe_case_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+    hipLaunchKernelGGL(k_bpe_case_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
+                       counts);
+  } else if (split) {
+    if (T->nfc)
+      hipLaunchKernelGGL(k_bpe_split_count_nfc, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
+                         counts);
+    else
+      hipLaunchKernelGGL(k_bpe_split_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
     hipLaunchKernelGGL(k_bpe_split_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
                        counts);
   } else {

@@ -13,7 +13,10 @@
 #include "../common/badwords.h"
 #include "../common/bpe.h"
 #include "../common/bpe_split.h"
+#include "../common/bpe_case.h"
 #include "../common/bpe_classes.inc"
+#include "../common/nfc_qc.inc"
+#include "../common/bpe_case_classes.inc"
 #include "../common/wordpiece.h"
 #include "../common/wp_classes.inc"
 #include "../common/wp_fold.inc"
@@ -366,15 +369,16 @@ PYBIND11_MODULE(_tbhost, m) {
                         py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
                         int nthreads, int64_t chunk, int kind, bool ignore_merges,
                         py::array_t<uint64_t, py::array::c_style> vslots, uint32_t vmask,
-                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest) {
+                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest, bool nfc) {
     // host emulation of k_bpe_count / k_bpe_split_count (kind: BpeKind): per document the token
     // count, or kBpeHost. chunk > 0: the wave split — the pre-tokens starting in each chunk-byte
-    // range counted independently (bpe_count_range), as the kernel's lanes do
-    const bool split = kind == kBpeSplitA || kind == kBpeSplitB;
+    // range counted independently (bpe_count_range), as the kernel's lanes do. nfc: behind the NFC
+    // gate (bpe_nfc_range, per range in the chunk mode), as k_bpe_split_count_nfc
+    const bool split = bpe_kind_split(kind);
     if (byte_id.size() != 256 || (size_t)keys.size() != (size_t)mask + 1 || vals.size() != keys.size() ||
         (!split && kind != kBpeGpt2) || added_off.size() > (size_t)(split ? kBpeSplitMaxAdded : kBpeMaxAdded) + 1 ||
         (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size())) ||
-        !std::is_sorted(added_off.begin(), added_off.end()) || (ignore_merges && !split) ||
+        !std::is_sorted(added_off.begin(), added_off.end()) || (ignore_merges && !split) || (nfc && !split) ||
         (ignore_merges && ((size_t)vslots.size() != 2 * ((size_t)vmask + 1) || vlongest < 1)))
       throw std::invalid_argument("bpe_count: operand shapes");
     if (ignore_merges)  // every listed entry lies in the pool
@@ -407,6 +411,11 @@ PYBIND11_MODULE(_tbhost, m) {
     }
     T.kind = kind;
     T.post_add = post_add;
+    T.ccls1 = TB_BPE_CASE_STAGE1;
+    T.ccls2 = TB_BPE_CASE_STAGE2;
+    T.nfc1 = TB_NFC_QC_STAGE1;
+    T.nfc2 = TB_NFC_QC_STAGE2;
+    T.nfc = nfc;
     const uint8_t* d = data.data();
     const int64_t* o = off.data();
     auto run = [&](auto policy) {
@@ -437,6 +446,10 @@ PYBIND11_MODULE(_tbhost, m) {
             int64_t tot = T.post_add;
             bool bad = T.n_added && P::has_added(T, b, n, 0, n);
             for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
+              if (T.nfc && bpe_nfc_range(T, b, n, s0, std::min(n, s0 + chunk)) != 1) {
+                bad = true;
+                break;
+              }
               const int64_t x = bpe_count_range<true, P>(T, b, n, s0, std::min(n, s0 + chunk), BpeArr{cbuf, 1},
                                                          BpeArr{rbuf, 1}, on_long);
               if (x < 0) bad = true;
@@ -447,27 +460,44 @@ PYBIND11_MODULE(_tbhost, m) {
         });
       for (auto& x : th) x.join();
     };
-    if (split) run(BpeSplit{});
+    if (bpe_kind_case(kind)) run(BpeCase{});
+    else if (split) run(BpeSplit{});
     else run(BpeGpt2{});
     return to_numpy(std::move(out));
   }, py::arg("data"), py::arg("off"), py::arg("byte_id"), py::arg("keys"), py::arg("vals"), py::arg("mask"),
         py::arg("added"), py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0,
         py::arg("kind") = 0, py::arg("ignore_merges") = false,
         py::arg("vslots") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("vmask") = 0,
-        py::arg("vpool") = py::array_t<uint8_t, py::array::c_style>(0), py::arg("vlongest") = 0);
+        py::arg("vpool") = py::array_t<uint8_t, py::array::c_style>(0), py::arg("vlongest") = 0,
+        py::arg("nfc") = false);
+  m.def("nfc_qc", []() {
+    // the NFC gate's two-stage table (csrc/common/nfc_qc.inc)
+    std::vector<uint8_t> t1(TB_NFC_QC_STAGE1, TB_NFC_QC_STAGE1 + sizeof(TB_NFC_QC_STAGE1));
+    std::vector<uint8_t> t2(TB_NFC_QC_STAGE2, TB_NFC_QC_STAGE2 + sizeof(TB_NFC_QC_STAGE2));
+    return py::make_tuple(to_numpy(std::move(t1)), to_numpy(std::move(t2)));
+  });
+  m.def("bpe_case_classes", []() {
+    std::vector<uint16_t> c1(TB_BPE_CASE_STAGE1, TB_BPE_CASE_STAGE1 + sizeof(TB_BPE_CASE_STAGE1) / 2);
+    std::vector<uint32_t> c2(TB_BPE_CASE_STAGE2, TB_BPE_CASE_STAGE2 + sizeof(TB_BPE_CASE_STAGE2) / 4);
+    return py::make_tuple(to_numpy(std::move(c1)), to_numpy(std::move(c2)));
+  });
   m.def("bpe_split_ends", [](py::bytes text, int kind) -> py::object {
-    // the pre-tokens of pattern A / B (bpe_split_next_token): their end offsets in bytes, None on
-    // invalid UTF-8 (for tests and tools that compare the rules with the library's Split)
-    if (kind != kBpeSplitA && kind != kBpeSplitB) throw std::invalid_argument("bpe_split_ends: kind");
+    // the pre-tokens of pattern A / B (bpe_split_next_token) or C / D (bpe_case_next_token): their
+    // end offsets in bytes, None on invalid UTF-8 (for tests and tools that compare the rules with
+    // the library's Split)
+    if (!bpe_kind_split(kind)) throw std::invalid_argument("bpe_split_ends: kind");
     const std::string s = text;
     DevBpe T{};
     T.cls1 = TB_BPE_CLS_STAGE1;
     T.cls2 = TB_BPE_CLS_STAGE2;
+    T.ccls1 = TB_BPE_CASE_STAGE1;
+    T.ccls2 = TB_BPE_CASE_STAGE2;
     T.kind = kind;
     std::vector<int64_t> ends;
     const int64_t n = (int64_t)s.size();
     for (int64_t p = 0; p < n;) {
-      const int64_t e = bpe_split_next_token(T, reinterpret_cast<const uint8_t*>(s.data()), n, p);
+      const uint8_t* u = reinterpret_cast<const uint8_t*>(s.data());
+      const int64_t e = bpe_kind_case(kind) ? bpe_case_next_token(T, u, n, p) : bpe_split_next_token(T, u, n, p);
       if (e <= p) return py::none();
       ends.push_back(e);
       p = e;

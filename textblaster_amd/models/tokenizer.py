@@ -14,8 +14,11 @@ table plus the byte ids, which the device pipeline counts with (csrc/common/bpe.
 and ``count_native`` runs on the host (same algorithm; documents it cannot count exactly are
 counted by ``tokenizers``). So do the byte-level BPE tokenizers serialised as
 Split(regex) + ByteLevel(use_regex=false) with the Llama-3 / cl100k_base pattern or Qwen2's
-(csrc/common/bpe_split.h, k_bpe_split_count): their spec also carries the vocabulary's raw bytes
-for ``ignore_merges`` and up to 1024 added tokens. WordPiece tokenizers (BertNormalizer +
+(csrc/common/bpe_split.h, k_bpe_split_count), or with the case-aware pattern of o200k_base or of
+Mistral's Tekken (csrc/common/bpe_case.h, k_bpe_case_count): their spec also carries the vocabulary's raw bytes
+for ``ignore_merges`` and up to 1024 added tokens. Real Qwen2 files carry an NFC normalizer: their
+spec has ``nfc`` set, and the counter (k_bpe_split_count_nfc) counts the documents that the Unicode
+quick check proves NFC leaves unchanged and returns -2 for the rest. WordPiece tokenizers (BertNormalizer +
 BertPreTokenizer, the BERT family) get a :class:`WordPieceSpec` instead (:meth:`TokenCounterModel.wordpiece_spec`): the vocabulary as an
 open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count). With ``lowercase``
 or ``strip_accents`` the device path counts with :meth:`TokenCounterModel.wordpiece_fold_spec`, which
@@ -81,26 +84,33 @@ class BpeSpec:
     added_off: List[int]   # [n_added + 1]
     post_add: int          # tokens the post-processor adds
     # the split-regex family (csrc/common/bpe_split.h); GPT-2 keeps the defaults
-    kind: int = 0                          # BPE_GPT2 / BPE_SPLIT_A / BPE_SPLIT_B
+    kind: int = 0                          # BPE_GPT2 / BPE_SPLIT_A / BPE_SPLIT_B / BPE_CASE_C / BPE_CASE_D
     ignore_merges: bool = False
     vslots: Optional[np.ndarray] = None    # uint64 [2 * (vmask + 1)]: the vocabulary's raw bytes, WpSlot pairs
     vmask: int = 0
     vpool: Optional[np.ndarray] = None     # uint8: the entries' raw bytes
     vlongest: int = 0                      # bytes of the longest entry
     added_mask: Optional[np.ndarray] = None  # uint64 [4]: first bytes of the added tokens
+    nfc: bool = False                      # the normalizer is NFC: documents it may change come back -2
 
 
-BPE_GPT2, BPE_SPLIT_A, BPE_SPLIT_B = 0, 1, 2  # csrc/common/bpe.h BpeKind
+BPE_GPT2, BPE_SPLIT_A, BPE_SPLIT_B, BPE_CASE_C, BPE_CASE_D = 0, 1, 2, 3, 4  # csrc/common/bpe.h BpeKind
 SPLIT_MAX_ADDED, SPLIT_MAX_ADDED_BYTES = 1024, 65536  # kBpeSplitMaxAdded, kBpeSplitMaxAddedBytes
 # the Split patterns counted on the device: Llama-3 / cl100k_base, and the Qwen2 family
 SPLIT_PATTERN_A = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
                    r"|\s*[\r\n]+|\s+(?!\S)|\s+")
 SPLIT_PATTERN_B = SPLIT_PATTERN_A.replace(r"\p{N}{1,3}", r"\p{N}")
+# the case-aware patterns (csrc/common/bpe_case.h): o200k_base, and Mistral's Tekken
+SPLIT_PATTERN_C = (r"[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?"
+                   r"|[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?"
+                   r"|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+")
+SPLIT_PATTERN_D = SPLIT_PATTERN_C.replace(r"(?i:'s|'t|'re|'ve|'m|'ll|'d)?", "").replace(r"\p{N}{1,3}", r"\p{N}")
+SPLIT_PATTERNS = {"A": SPLIT_PATTERN_A, "B": SPLIT_PATTERN_B, "C": SPLIT_PATTERN_C, "D": SPLIT_PATTERN_D}
 
 
 def _split_kind(pt) -> Optional[int]:
-    """BPE_SPLIT_A / _B when the pre-tokenizer is exactly Sequence[Split(Regex(A or B), Isolated),
-    ByteLevel(add_prefix_space=false, use_regex=false)], else None."""
+    """BPE_SPLIT_A / _B / BPE_CASE_C / _D when the pre-tokenizer is exactly Sequence[Split(Regex(A, B,
+    C or D), Isolated), ByteLevel(add_prefix_space=false, use_regex=false)], else None."""
     if not isinstance(pt, dict) or pt.get("type") != "Sequence":
         return None
     pts = pt.get("pretokenizers") or []
@@ -114,7 +124,8 @@ def _split_kind(pt) -> Optional[int]:
     pat = sp.get("pattern")
     if not isinstance(pat, dict) or set(pat) != {"Regex"}:
         return None
-    return {SPLIT_PATTERN_A: BPE_SPLIT_A, SPLIT_PATTERN_B: BPE_SPLIT_B}.get(pat["Regex"])
+    return {SPLIT_PATTERN_A: BPE_SPLIT_A, SPLIT_PATTERN_B: BPE_SPLIT_B, SPLIT_PATTERN_C: BPE_CASE_C,
+            SPLIT_PATTERN_D: BPE_CASE_D}.get(pat["Regex"])
 
 
 def _post_add(pp) -> Optional[int]:
@@ -148,23 +159,33 @@ def _post_add(pp) -> Optional[int]:
     return None
 
 
-def build_bpe_spec(tj: dict) -> Optional[BpeSpec]:
+def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
     """BpeSpec of a parsed tokenizer.json, or None when the tokenizer is not a byte-level BPE the
-    device counter reproduces exactly: no normalizer, plain BPE merges, no truncation / padding, a
-    known post-processor, and as pre-tokenizer either GPT-2's ByteLevel regex without prefix space
-    (at most MAX_ADDED added tokens, no ignore_merges) or Split(pattern A / B) + ByteLevel without
-    regex (Llama-3, cl100k_base, Qwen2: ignore_merges allowed, no byte_fallback, at most
-    SPLIT_MAX_ADDED added tokens of SPLIT_MAX_ADDED_BYTES bytes together)."""
+    device counter reproduces exactly: plain BPE merges, no truncation / padding, a known
+    post-processor, and as pre-tokenizer either GPT-2's ByteLevel regex without prefix space (no
+    normalizer, at most MAX_ADDED added tokens, no ignore_merges) or Split(pattern A / B / C / D) +
+    ByteLevel without regex (Llama-3, cl100k_base, Qwen2, o200k_base, Tekken: ignore_merges allowed, no byte_fallback, at most
+    SPLIT_MAX_ADDED added tokens of SPLIT_MAX_ADDED_BYTES bytes together).
+
+    A tokenizer with a normalizer has no spec, unless ``nfc`` is set (as :meth:`TokenCounterModel.bpe_spec`
+    does): then a split-regex tokenizer whose normalizer is exactly ``{"type": "NFC"}`` and that has
+    no added token matched on normalised text gets a spec with ``nfc`` on, whose counter returns -2
+    for every document it cannot prove NFC leaves unchanged."""
     from .. import native
 
     m = tj.get("model") or {}
     if m.get("type") != "BPE" or m.get("dropout") not in (None, 0, 0.0) or m.get("continuing_subword_prefix") \
             or m.get("end_of_word_suffix"):
         return None
-    if tj.get("normalizer") is not None or tj.get("truncation") is not None or tj.get("padding") is not None:
+    if tj.get("truncation") is not None or tj.get("padding") is not None:
         return None
     pt = tj.get("pre_tokenizer")
     kind = _split_kind(pt)
+    nz = tj.get("normalizer")
+    if nz is not None and (not nfc or nz != {"type": "NFC"} or kind is None
+                           or any(t.get("normalized") for t in tj.get("added_tokens") or [] if t.get("content"))):
+        return None
+    nfc = nz is not None
     if kind is None:
         kind = BPE_GPT2
         if m.get("ignore_merges"):
@@ -213,6 +234,7 @@ def build_bpe_spec(tj: dict) -> Optional[BpeSpec]:
     if off[-1] > SPLIT_MAX_ADDED_BYTES:
         return None
     spec.kind = kind
+    spec.nfc = nfc
     spec.ignore_merges = bool(m.get("ignore_merges"))
     spec.added_mask = native.host().bpe_added_mask(spec.added, spec.added_off)
     if spec.ignore_merges:
@@ -327,10 +349,11 @@ class TokenCounterModel:
         return [len(e.tokens) for e in encs]
 
     def bpe_spec(self) -> Optional[BpeSpec]:
-        """Device/native tables when this is a byte-level BPE tokenizer (else None); built once."""
+        """Device/native tables when this is a byte-level BPE tokenizer (else None; behind an NFC
+        normalizer the spec of the NFC gate); built once."""
         if self._spec is False:
             with open(self.path, encoding="utf-8") as f:
-                self._spec = build_bpe_spec(json.load(f))
+                self._spec = build_bpe_spec(json.load(f), nfc=True)
         return self._spec
 
     def wordpiece_spec(self) -> Optional[WordPieceSpec]:
@@ -360,8 +383,8 @@ class TokenCounterModel:
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
         """Token counts of packed UTF-8 documents with the native counter of whichever spec the
         tokenizer has (host emulation of k_bpe_count / k_wp_count); documents it returns -2 for
-        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, WordPiece text with a code
-        point whose place NFD may change under strip_accents) are counted by ``tokenizers``."""
+        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, text that an NFC normalizer
+        may change, WordPiece text with a code point whose place NFD may change under strip_accents) are counted by ``tokenizers``."""
         from .. import native
 
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -391,7 +414,7 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
     none64, none8 = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint8)
     return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
                        nthreads, chunk, sp.kind, sp.ignore_merges, none64 if sp.vslots is None else sp.vslots,
-                       sp.vmask, none8 if sp.vpool is None else sp.vpool, sp.vlongest)
+                       sp.vmask, none8 if sp.vpool is None else sp.vpool, sp.vlongest, sp.nfc)
 
 
 def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
@@ -453,23 +476,25 @@ def train_synthetic_bpe(path: str, vocab_size: int = 50257, n_docs: int = 20000,
 
 
 def train_synthetic_split_bpe(path: str, vocab_size: int = 32000, pattern: str = "A", ignore_merges: bool = True,
-                              n_added: int = 256, n_docs: int = 20000, seed: int = 1) -> str:
+                              n_added: int = 256, n_docs: int = 20000, seed: int = 1, nfc: bool = False) -> str:
     """Train a Llama-3-format byte-level BPE tokenizer on the synthetic Zipf corpus and save it as
-    ``path`` (kept if it already exists): pre-tokenizer Sequence[Split(pattern A or B, Isolated),
+    ``path`` (kept if it already exists): pre-tokenizer Sequence[Split(pattern A, B, C or D, Isolated),
     ByteLevel(use_regex=false)], post-processor Sequence[ByteLevel, TemplateProcessing] that puts
     ``<|begin_of_text|>`` in front, ``ignore_merges`` as given, and ``n_added`` added tokens
     (``<|begin_of_text|>``, ``<|end_of_text|>`` and reserved specials) after the ``vocab_size``
-    model entries, as Llama-3 lays them out. The stand-in for Llama-3 / cl100k_base / Qwen2, which
+    model entries, as Llama-3 lays them out; ``nfc`` adds the NFC normalizer of the Qwen2 files. The stand-in for Llama-3 / cl100k_base / Qwen2, which
     cannot be downloaded here; the counts differ from theirs, the work per byte is of the same kind."""
     if os.path.isfile(path):
         return path
-    from tokenizers import Regex, Tokenizer, decoders, models, pre_tokenizers, processors, trainers
+    from tokenizers import Regex, Tokenizer, decoders, models, normalizers, pre_tokenizers, processors, trainers
 
     from ..utils import synth
 
-    pat = {"A": SPLIT_PATTERN_A, "B": SPLIT_PATTERN_B}[pattern]
+    pat = SPLIT_PATTERNS[pattern]
     texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
     tok = Tokenizer(models.BPE(ignore_merges=ignore_merges))
+    if nfc:
+        tok.normalizer = normalizers.NFC()
     tok.pre_tokenizer = pre_tokenizers.Sequence([
         pre_tokenizers.Split(Regex(pat), behavior="isolated", invert=False),
         pre_tokenizers.ByteLevel(add_prefix_space=False, use_regex=False)])

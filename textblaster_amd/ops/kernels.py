@@ -161,15 +161,17 @@ class DevBpe(ctypes.Structure):
     """csrc/common/bpe.h DevBpe (checked against tb_sizeof_bpe)."""
     _fields_ = [("byte_id", _P), ("keys", _P), ("vals", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
                 ("mask", _U32), ("n_added", _I32), ("added_off", _I32 * 9), ("post_add", _I32),
-                ("aoff", _P), ("vslots", _P), ("vpool", _P), ("amask", ctypes.c_uint64 * 4),
-                ("vmask", _U32), ("vlongest", _I32), ("kind", _I32), ("ignore_merges", _I32)]
+                ("aoff", _P), ("vslots", _P), ("vpool", _P), ("nfc1", _P), ("nfc2", _P),
+                ("ccls1", _P), ("ccls2", _P),
+                ("amask", ctypes.c_uint64 * 4), ("vmask", _U32), ("vlongest", _I32), ("kind", _I32),
+                ("ignore_merges", _I32), ("nfc", _I32), ("pad_", _I32)]
 
 
 class BpeTables:
     """A byte-level BPE tokenizer's tables in HBM (models/tokenizer.py BpeSpec) and the kernel's
     parameter block pointing at them."""
 
-    def __init__(self, spec, cls_tables):
+    def __init__(self, spec, cls_tables, nfc_tables=None, case_tables=None):
         from . import hiprt
 
         self.arrays = [hiprt.to_device(a) for a in (spec.byte_id, spec.keys, spec.vals, cls_tables[0], cls_tables[1],
@@ -200,6 +202,18 @@ class BpeTables:
                 self.arrays += [hiprt.to_device(spec.vslots), hiprt.to_device(spec.vpool)]
                 st.vslots, st.vpool = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
                 st.vmask, st.vlongest, st.ignore_merges = spec.vmask, spec.vlongest, 1
+        if spec.kind in (3, 4):
+            # the case-aware patterns' class table (csrc/common/bpe_case_classes.inc)
+            if case_tables is None:
+                raise DeviceError("bpe: the case-aware patterns need their class table")
+            self.arrays += [hiprt.to_device(case_tables[0]), hiprt.to_device(case_tables[1])]
+            st.ccls1, st.ccls2 = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
+        if spec.nfc:
+            # the NFC gate's table (csrc/common/nfc_qc.inc)
+            if not split or nfc_tables is None:
+                raise DeviceError("bpe: the NFC gate needs a split-regex spec and its table")
+            self.arrays += [hiprt.to_device(nfc_tables[0]), hiprt.to_device(nfc_tables[1])]
+            st.nfc1, st.nfc2, st.nfc = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr(), 1
         self.struct = st
 
 
@@ -488,10 +502,14 @@ class Kernels:
 
         if self.lib.tb_sizeof_bpe() != ctypes.sizeof(DevBpe):
             raise DeviceError("libtbhip.so DevBpe layout differs from the binding; rebuild")
-        return BpeTables(spec, native.host().bpe_classes())
+        h = native.host()
+        return BpeTables(spec, h.bpe_classes(), h.nfc_qc() if spec.nfc else None,
+                         h.bpe_case_classes() if spec.kind in (3, 4) else None)
 
     def bpe_count(self, tabs: BpeTables, text, off, n_dev, n_max: int, counts):
-        """k_bpe_count + k_bpe_long, or k_bpe_split_count + k_bpe_split_long for a split-regex spec:
+        """k_bpe_count + k_bpe_long, or for a split-regex spec k_bpe_split_count + k_bpe_split_long
+        (k_bpe_case_count + k_bpe_case_long for the case-aware patterns; the _nfc count kernels behind
+        the NFC gate):
         token counts of documents k < min(n_dev[0], n_max) (csrc/hip/bpe.hip); ``n_dev``: optional
         one-element int64 device array (the kept count of K16)."""
         if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:

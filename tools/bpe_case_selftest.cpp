@@ -1,0 +1,344 @@
+// Standalone self-test of the case-aware split-regex BPE token counter (csrc/common/bpe_case.h) and
+// the NFC gate (csrc/common/bpe.h bpe_nfc_range), built with AddressSanitizer +
+// UndefinedBehaviorSanitizer by tests/test_bpe_case_sanitizers.py:
+//
+//   * a small merge list in the open-addressed pair table, its vocabulary in the whole-piece table
+//     (wp_fill_slots), two added tokens behind the first-byte mask; patterns C and D, ignore_merges
+//     on and off, the NFC gate on and off
+//   * adversarial documents in exactly sized heap buffers (a lookahead past the end is a report):
+//     case runs with caseless letters and marks, contractions as suffixes in both cases and with
+//     U+017F, number runs, punctuation runs with '/' and newlines, newlines in whitespace runs,
+//     2-4-byte code points, marks in and out of canonical order, code points that may compose,
+//     pre-tokens around 64 and 2048 bytes, added-token text, truncated and stray UTF-8
+//   * bpe_count_doc<BpeCase> against a plain std::string implementation: the pattern's alternatives
+//     tried in order with their backtracking over the decoded code points (the greedy Up* gives
+//     back one code point at a time), lowest-rank-first merges over strings, and the quick check
+//     as one pass over the decoded code points
+//   * and against the sum of bpe_count_range<true, BpeCase> behind bpe_nfc_range over chunks of 1,
+//     2, 3, 5, 16, 17 and 64 bytes (the kernels' lane split)
+//
+// Exits non-zero on any mismatch; sanitizer reports abort the run.
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <random>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../csrc/common/bpe_case.h"
+#include "../csrc/common/bpe_case_classes.inc"
+#include "../csrc/common/bpe_classes.inc"
+#include "../csrc/common/nfc_qc.inc"
+
+using namespace tb;
+
+static int g_fail = 0;
+
+struct Tok {
+  std::vector<uint32_t> byte_id;
+  std::vector<uint64_t> keys, vals;
+  std::map<std::pair<std::string, std::string>, int> rank;  // the reference's view of the merges
+  std::map<std::string, uint32_t> ids;
+  std::set<std::string> vocab;
+  std::vector<uint8_t> vpool;
+  std::vector<int64_t> voff{0};
+  std::vector<WpSlot> vslots;
+  std::string added = "<|bot|><eot>";
+  std::vector<int32_t> aoff{0, 7, 12};
+  DevBpe T{};
+
+  Tok(int kind, bool ignore_merges, bool nfc, const std::vector<std::pair<std::string, std::string>>& merges) {
+    for (int i = 0; i < 256; ++i) {
+      byte_id.push_back((uint32_t)i);
+      ids[std::string(1, (char)i)] = (uint32_t)i;
+      vocab.insert(std::string(1, (char)i));
+    }
+    size_t cap = 16;
+    while (cap < 2 * merges.size()) cap <<= 1;
+    keys.assign(cap, kBpeEmpty);
+    vals.assign(cap, ~0ull);
+    for (size_t i = 0; i < merges.size(); ++i) {
+      const std::string ab = merges[i].first + merges[i].second;
+      const uint32_t next_id = (uint32_t)ids.size();
+      if (!ids.count(ab)) ids[ab] = next_id;
+      rank[merges[i]] = (int)i;
+      vocab.insert(ab);
+      const uint64_t key = ((uint64_t)ids[merges[i].first] << 32) | ids[merges[i].second];
+      uint64_t h = bpe_hash(key) & (cap - 1);
+      while (keys[h] != kBpeEmpty) h = (h + 1) & (cap - 1);
+      keys[h] = key;
+      vals[h] = ((uint64_t)i << 32) | ids[ab];
+    }
+    vocab.insert("abc");  // an entry no merge order reaches ("b c" goes first)
+    vocab.insert(std::string(70, '-'));  // and one over the lanes' 64-byte arrays
+    std::vector<uint8_t> cont;
+    for (const std::string& w : vocab) {
+      vpool.insert(vpool.end(), w.begin(), w.end());
+      voff.push_back((int64_t)vpool.size());
+      cont.push_back(0);
+    }
+    size_t vcap = 16;
+    while (vcap < 2 * cont.size()) vcap <<= 1;
+    vslots.assign(vcap, WpSlot{0, kWpEmpty});
+    T.vlongest = (int32_t)wp_fill_slots(vpool.data(), voff.data(), cont.data(), cont.size(), vslots.data(), vcap - 1);
+    T.vslots = reinterpret_cast<const uint64_t*>(vslots.data());
+    T.vpool = vpool.data();
+    T.vmask = (uint32_t)(vcap - 1);
+    T.byte_id = byte_id.data();
+    T.keys = keys.data();
+    T.vals = vals.data();
+    T.mask = (uint32_t)(cap - 1);
+    T.cls1 = TB_BPE_CLS_STAGE1;
+    T.cls2 = TB_BPE_CLS_STAGE2;
+    T.ccls1 = TB_BPE_CASE_STAGE1;
+    T.ccls2 = TB_BPE_CASE_STAGE2;
+    T.nfc1 = TB_NFC_QC_STAGE1;
+    T.nfc2 = TB_NFC_QC_STAGE2;
+    T.nfc = nfc;
+    T.added = reinterpret_cast<const uint8_t*>(added.data());
+    T.aoff = aoff.data();
+    T.n_added = 2;
+    bpe_added_mask(T.added, T.aoff, T.n_added, T.amask);
+    T.post_add = 1;
+    T.kind = kind;
+    T.ignore_merges = ignore_merges;
+  }
+};
+
+struct Cp {
+  int32_t c;
+  int k;
+  int64_t at;
+};
+
+// the pattern's alternatives in order, with their backtracking, over the decoded code points:
+// the index after the match that starts at i
+static size_t ref_match(const std::vector<Cp>& d, size_t i, int kind) {
+  const size_t m = d.size();
+  auto is = [&](size_t j, int k) { return j < m && d[j].k == k; };
+  auto nl = [&](size_t j) { return j < m && (d[j].c == '\r' || d[j].c == '\n'); };
+  auto up = [&](size_t j) { return is(j, BPC_U) || is(j, BPC_B) || is(j, BPC_M); };
+  auto lo = [&](size_t j) { return is(j, BPC_LOW) || is(j, BPC_B) || is(j, BPC_M); };
+  auto letter = [&](size_t j) { return is(j, BPC_U) || is(j, BPC_LOW) || is(j, BPC_B); };
+  auto low = [&](size_t j) -> int32_t {
+    if (j >= m) return -1;
+    if (d[j].c == 0x17F) return 's';
+    return (d[j].c >= 'A' && d[j].c <= 'Z') ? d[j].c + 32 : d[j].c;
+  };
+  // (?i:'s|'t|'re|'ve|'m|'ll|'d)? of pattern C
+  auto suffix = [&](size_t j) -> size_t {
+    if (kind != kBpeCaseC || j >= m || d[j].c != '\'') return j;
+    for (const char* w : {"s", "t", "re", "ve", "m", "ll", "d"}) {
+      const size_t L = std::strlen(w);
+      bool ok = true;
+      for (size_t q = 0; q < L; ++q) ok = ok && low(j + 1 + q) == w[q];
+      if (ok) return j + 1 + L;
+    }
+    return j;
+  };
+  // [^\r\n\p{L}\p{N}]?Up*Lo+S?
+  for (int opt = 1; opt >= 0; --opt) {
+    size_t j = i;
+    if (opt) {
+      if (nl(j) || letter(j) || is(j, BPC_N)) continue;
+      ++j;
+    }
+    size_t k = j;
+    while (up(k)) ++k;
+    for (size_t u = k + 1; u-- > j;) {  // Up* gives back one code point at a time
+      size_t v = u;
+      while (lo(v)) ++v;
+      if (v > u) return suffix(v);
+    }
+  }
+  // [^\r\n\p{L}\p{N}]?Up+Lo*S?
+  for (int opt = 1; opt >= 0; --opt) {
+    size_t j = i;
+    if (opt) {
+      if (nl(j) || letter(j) || is(j, BPC_N)) continue;
+      ++j;
+    }
+    size_t k = j;
+    while (up(k)) ++k;
+    if (k == j) continue;
+    while (lo(k)) ++k;
+    return suffix(k);
+  }
+  // \p{N}{1,3} / \p{N}
+  if (is(i, BPC_N)) {
+    size_t j = i + 1;
+    while (j < i + (kind == kBpeCaseC ? 3 : 1) && is(j, BPC_N)) ++j;
+    return j;
+  }
+  //  ?[^\s\p{L}\p{N}]+[\r\n/]*
+  for (int opt = 1; opt >= 0; --opt) {
+    size_t j = i;
+    if (opt) {
+      if (d[j].c != ' ') continue;
+      ++j;
+    }
+    if (!is(j, BPC_O) && !is(j, BPC_M)) continue;
+    while (is(j, BPC_O) || is(j, BPC_M)) ++j;
+    while (nl(j) || (j < m && d[j].c == '/')) ++j;
+    return j;
+  }
+  size_t k = i;  // the greedy \s* / \s+
+  while (is(k, BPC_W)) ++k;
+  // \s*[\r\n]+
+  for (size_t p = k + 1; p-- > i;) {
+    size_t q = p;
+    while (nl(q)) ++q;
+    if (q > p) return q;
+  }
+  // \s+(?!\S)
+  for (size_t p = k; p > i; --p)
+    if (p == m || d[p].k == BPC_W) return p;
+  // \s+
+  return k > i ? k : i;
+}
+
+static int64_t ref_merge(const Tok& V, const std::string& w) {
+  if (V.T.ignore_merges && V.vocab.count(w)) return 1;
+  std::vector<std::string> s;
+  for (char ch : w) s.emplace_back(1, ch);
+  for (;;) {
+    int best = 1 << 30;
+    size_t bi = 0;
+    for (size_t i = 0; i + 1 < s.size(); ++i) {
+      const auto it = V.rank.find({s[i], s[i + 1]});
+      if (it != V.rank.end() && it->second < best) { best = it->second; bi = i; }
+    }
+    if (best == 1 << 30) break;
+    s[bi] += s[bi + 1];
+    s.erase(s.begin() + (long)bi + 1);
+  }
+  return (int64_t)s.size();
+}
+
+static int32_t reference(const Tok& V, const uint8_t* b, int64_t n) {
+  const std::string doc(reinterpret_cast<const char*>(b), (size_t)n);
+  if (doc.find("<|bot|>") != std::string::npos || doc.find("<eot>") != std::string::npos) return kBpeHost;
+  std::vector<Cp> d;
+  for (int64_t i = 0; i < n;) {
+    int l;
+    const int32_t c = bpe_decode(b, i, n, &l);
+    if (c < 0) return kBpeHost;
+    d.push_back({c, bpe_case_cls(V.T, (uint32_t)c), i});
+    i += l;
+  }
+  if (V.T.nfc) {  // the quick check in one pass
+    int prev = 0;
+    for (const Cp& x : d) {
+      const int e = x.c < 0x300 ? 0 : TB_NFC_QC_STAGE2[TB_NFC_QC_STAGE1[x.c >> 7] * 128 + (x.c & 127)];
+      if (e == 255 || (e != 0 && prev > e)) return kBpeHost;
+      prev = e;
+    }
+  }
+  int64_t total = V.T.post_add;
+  for (size_t i = 0; i < d.size();) {
+    const size_t e = ref_match(d, i, V.T.kind);
+    if (e <= i) return kBpeHost;
+    const int64_t a = d[i].at, z = e < d.size() ? d[e].at : n;
+    if (z - a > kBpeMaxLong) return kBpeHost;
+    total += ref_merge(V, doc.substr((size_t)a, (size_t)(z - a)));
+    i = e;
+  }
+  return (int32_t)total;
+}
+
+static std::string random_doc(std::mt19937_64& rng) {
+  static const char* parts[] = {"A", "B", "ABC", "Ab", "DEF", "/", "\xC7\x85", "\xE3\x81\x82", "\xCA\xB0", "\xC4\xB0",
+                                "\xD6\xB0", "\xD6\xB4", "\xE0\xA4\xBC", "\xE1\x85\xA1", "\xCC\xA3",
+                                "a", "b", "c", "abc", "ab", "the", "'", "s", "S", "t", "re", "RE", "vE", "ll", "LL", "m", "d",
+                                "\xC5\xBF", "\xE2\x84\xAA", " ", " ", "  ", "\n", "\r", "\r\n", "\t", "\xC2\xA0",
+                                "\xE3\x80\x80", "\xC2\x85", "1", "42", "1234567", "\xC2\xB2", "\xD9\xA3", "!", "?", "...",
+                                "-", "_", "\xCC\x81", "\xC3\xA9", "\xE6\x97\xA5", "\xF0\x9F\x98\x80", "\xE2\x92\xB6",
+                                "\xCD\x85", "<|bo", "t|>", "<eo", "--------------------------------"};
+  static const char* broken[] = {"\xFF", "\xC3", "\x80", "\xE2\x82", "\xF0\x9F\x98", "\xED\xA0\x80", "\xC0\xAF", "<eot>"};
+  std::string s;
+  const int n = (int)(rng() % 60);
+  for (int i = 0; i < n; ++i) {
+    s += parts[rng() % (sizeof(parts) / sizeof(*parts))];
+    if (rng() % 97 == 0) s += broken[rng() % (sizeof(broken) / sizeof(*broken))];
+  }
+  return s;
+}
+
+static void run(const Tok& V, const char* name, int ndocs, uint64_t seed) {
+  std::mt19937_64 rng(seed);
+  std::vector<std::string> docs = {"", "'", "'s", "x'", "x'l", "x'L", "x'\xC5", "12", "1234", " ", " \n", "\n ", "! ",
+                                   " !", "abc", " abc", std::string(70, '-'), std::string(71, '-'),
+                                   "<|bot|>", "ab<eot>cd", std::string(2048, 'a'), std::string(2049, 'b'),
+                                   std::string(3000, ' ') + "x", "1234567,.;: 89!? 1234567,.;: 89!? 1234567,.;: 89!?",
+                                   "A\xE3\x81\x82" "B", "\xE3\x81\x82" "A\xE3\x81\x82" "B", "ABC", "!ABC", "AbcDEFgh",
+                                   "DON'T'S", "a'r!", "it'\xC5\xBF x", "ab\xCC\x81'll", "\xCC\x81" "abc", "1\xCC\x81",
+                                   "!\n/\nx", "\n/x", "a/b", "  \n  a", "\xCC\x81" "ABC", "!\xCC\x81" "a", "!!\xCC\x81" "a",
+                                   "a\xD6\xB4\xD6\xB0", "a\xD6\xB0\xD6\xB4", "ab'cd'ef'gh'ab'cd'ef'gh'ab'cd'ef'gh"};
+  for (int i = 0; i < 40; ++i)  // two marks out of order across every chunk edge
+    docs.push_back(std::string((size_t)i, 'a') + "\xD7\x90\xD6\xB4\xD6\xB0 tail");
+  for (int i = 0; i < 140; ++i) docs.push_back(std::string((size_t)i, 'a') + "\xC3\xA9" + "'LL\n \n1234 !x");
+  for (int i = 0; i < ndocs; ++i) docs.push_back(random_doc(rng));
+  std::vector<uint32_t> lc(kBpeMaxLong);
+  std::vector<uint64_t> lv(kBpeMaxLong);
+  std::vector<int32_t> lnx(kBpeMaxLong), lpv(kBpeMaxLong);
+  uint32_t cbuf[kBpeMaxWord], rbuf[kBpeMaxWord];
+  int host = 0;
+  for (const std::string& d : docs) {
+    const int64_t n = (int64_t)d.size();
+    std::unique_ptr<uint8_t[]> buf(new uint8_t[d.size()]);  // no slack: reads past n are reports
+    std::memcpy(buf.get(), d.data(), d.size());
+    const uint8_t* b = buf.get();
+    auto on_long = [&](int64_t s, int64_t e) -> int64_t {
+      if (e - s > kBpeMaxLong) return -1;
+      return bpe_word_long(V.T, b + s, (int)(e - s), lc.data(), lv.data(), lnx.data(), lpv.data());
+    };
+    const int32_t want = reference(V, b, n);
+    const int32_t got = bpe_count_doc<BpeCase>(V.T, b, n, BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
+    host += got == kBpeHost;
+    if (got != want) {
+      std::fprintf(stderr, "FAIL %s: doc of %lld bytes: %d, reference %d\n", name, (long long)n, got, want);
+      ++g_fail;
+    }
+    for (int64_t chunk : {1, 2, 3, 5, 16, 17, 64}) {
+      if (n > 4096 && chunk < 16) continue;  // (quadratic without a sync point)
+      int64_t tot = V.T.post_add;
+      bool bad = BpeCase::has_added(V.T, b, n, 0, n);
+      for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
+        if (V.T.nfc && bpe_nfc_range(V.T, b, n, s0, s0 + chunk < n ? s0 + chunk : n) != 1) {
+          bad = true;
+          break;
+        }
+        const int64_t x = bpe_count_range<true, BpeCase>(V.T, b, n, s0, s0 + chunk < n ? s0 + chunk : n,
+                                                          BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
+        if (x < 0) bad = true;
+        tot += x;
+      }
+      const int32_t split = bad ? kBpeHost : (int32_t)tot;
+      if (split != got) {
+        std::fprintf(stderr, "FAIL %s: chunk %lld: %d, whole %d\n", name, (long long)chunk, split, got);
+        ++g_fail;
+      }
+    }
+  }
+  std::printf("%s: %zu documents, %d to the host\n", name, docs.size(), host);
+}
+
+int main(int argc, char** argv) {
+  const int ndocs = argc > 1 ? std::atoi(argv[1]) : 2000;
+  const std::vector<std::pair<std::string, std::string>> merges = {
+      {"b", "c"}, {"a", "b"}, {"ab", "c"}, {"t", "h"}, {"th", "e"}, {" ", "a"}, {"-", "-"}, {"--", "--"}, {"'", "s"},
+      {"1", "2"}, {"12", "3"}, {"\xC3", "\xA9"}, {" ", " "}, {"a", "a"}, {"aa", "aa"}, {"\r", "\n"}, {"!", "\n"}};
+  int v = 0;
+  for (int kind : {(int)kBpeCaseC, (int)kBpeCaseD})
+    for (int im = 0; im < 2; ++im) {
+      const bool nfc = (kind == kBpeCaseC) == (im != 0);  // C + ignore_merges and D without: behind the gate
+      const Tok V(kind, im != 0, nfc, merges);
+      char name[64];
+      std::snprintf(name, sizeof name, "pattern %c, ignore_merges %d, nfc %d", kind == kBpeCaseC ? 'C' : 'D', im, (int)nfc);
+      run(V, name, ndocs, 7 + (uint64_t)v++);
+    }
+  std::printf("%d failures\n", g_fail);
+  return g_fail ? 1 : 0;
+}
