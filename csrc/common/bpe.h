@@ -36,7 +36,10 @@
 // The counting loops (bpe_count_span / _range / _doc) take the pre-tokenizer as a policy: BpeGpt2
 // below is the regex above; BpeSplit (bpe_split.h) is the Split(regex) + ByteLevel(use_regex=false)
 // layout of Llama-3, cl100k_base and Qwen2, with ignore_merges and added tokens kept in memory;
-// BpeCase (bpe_case.h) is the same layout with the case-aware pattern of o200k_base or Tekken.
+// BpeCase (bpe_case.h) is the same layout with the case-aware pattern of o200k_base or Tekken;
+// BpeSp (bpe_sp.h) is the character-level BPE of the SentencePiece conversions (Llama-2, Mistral,
+// Gemma), whose policy also supplies a pre-token's initial symbols (code points, <0xNN> byte
+// tokens for those outside the vocabulary, a prepended U+2581) in place of the byte-level ids.
 #pragma once
 #include "tb_common.h"
 
@@ -53,17 +56,20 @@ constexpr int32_t kBpeLong = -3;
 constexpr int kBpeMaxLong = 2048;  // longest pre-token merged on the device
 
 // the pre-tokenizer: GPT-2's ByteLevel regex, or Split(pattern) + ByteLevel(use_regex=false) with
-// pattern A / B (bpe_split.h) or the case-aware C / D (bpe_case.h)
-enum BpeKind : int { kBpeGpt2 = 0, kBpeSplitA = 1, kBpeSplitB = 2, kBpeCaseC = 3, kBpeCaseD = 4 };
+// pattern A / B (bpe_split.h) or the case-aware C / D (bpe_case.h); or none of them: the chunks of a
+// SentencePiece-style character-level BPE (bpe_sp.h)
+enum BpeKind : int { kBpeGpt2 = 0, kBpeSplitA = 1, kBpeSplitB = 2, kBpeCaseC = 3, kBpeCaseD = 4, kBpeSp = 5 };
 TB_HD bool bpe_kind_case(int kind) { return kind == kBpeCaseC || kind == kBpeCaseD; }
 TB_HD bool bpe_kind_split(int kind) { return kind == kBpeSplitA || kind == kBpeSplitB || bpe_kind_case(kind); }
+// the kinds whose added tokens sit in memory (aoff, amask; up to kBpeSplitMaxAdded)
+TB_HD bool bpe_kind_mem_added(int kind) { return bpe_kind_split(kind) || kind == kBpeSp; }
 constexpr int kBpeSplitMaxAdded = 1024;
 constexpr int kBpeSplitMaxAddedBytes = 65536;
 
 enum BpeCls : int { BPE_O = 0, BPE_L = 1, BPE_N = 2, BPE_W = 3 };
 
 struct DevBpe {
-  const uint32_t* byte_id;   // [256]: vocabulary id of each byte's byte-level character
+  const uint32_t* byte_id;   // [256]: vocabulary id of each byte's byte-level character (kBpeSp: of <0xNN>)
   const uint64_t* keys;      // [mask + 1]: (left id << 32 | right id), kBpeEmpty = free slot
   const uint64_t* vals;      // [mask + 1]: (rank << 32 | merged id)
   const uint16_t* cls1;      // bpe_classes.inc two-stage class table
@@ -88,7 +94,12 @@ struct DevBpe {
   int32_t kind;              // BpeKind
   int32_t ignore_merges;     // a pre-token that is a vocabulary entry is one token
   int32_t nfc;               // the normalizer is NFC: count only the documents it leaves unchanged
-  int32_t pad_;
+  // kBpeSp only (csrc/common/bpe_sp.h): the single-code-point vocabulary entries
+  int32_t sp_flags;          // BpeSpFlags: the prepend rule, a chunk at every space
+  const uint32_t* sp_ascii;  // [128]: id of each ASCII code point, kBpeSpNone = no entry
+  const uint64_t* sp_cp;     // [sp_mask + 1]: (code point << 32 | id) of the others, kBpeSpEmpty = free slot
+  uint32_t sp_mask;
+  uint32_t sp_id;            // id of U+2581, which U+0020 is counted as too
 };
 
 TB_HD uint64_t bpe_hash(uint64_t k) {
@@ -155,10 +166,25 @@ struct BpeArr {
   TB_HD uint32_t& operator[](int i) const { return p[i * stride]; }
 };
 
-// Tokens of one pre-token (its L <= kBpeMaxWord bytes) after the merges.
-TB_HD int bpe_word(const DevBpe& T, const uint8_t* w, int L, BpeArr c, BpeArr r) {
-  if (L <= 1) return L;
-  for (int i = 0; i < L; ++i) c[i] = T.byte_id[w[i]];
+// The initial symbols of a pre-token as a part of the pre-tokenizer policy. Byte-level BPE: one
+// symbol per byte and none without bytes (lead); BpeSp (bpe_sp.h) decodes code points instead.
+struct BpeByteLevel {
+  static constexpr bool kByteSymbols = true;
+  static TB_HD int lead(const DevBpe&, const uint8_t*, int64_t, int64_t) { return 0; }
+};
+struct BpeGpt2;
+
+// Tokens of one pre-token (its L bytes and lead symbols in front of them, L + lead <= kBpeMaxWord)
+// after the merges.
+template <class P = BpeGpt2>
+TB_HD int bpe_word(const DevBpe& T, const uint8_t* w, int L, BpeArr c, BpeArr r, int lead = 0) {
+  if constexpr (P::kByteSymbols) {
+    if (L <= 1) return L;
+    for (int i = 0; i < L; ++i) c[i] = T.byte_id[w[i]];
+  } else {
+    L = P::symbols(T, w, L, lead, c);
+    if (L <= 1) return L;
+  }
   for (int i = 0; i + 1 < L; ++i) r[i] = (uint32_t)(bpe_lookup(T, c[i], c[i + 1]) >> 32);
   int m = L;
   while (m > 1) {
@@ -185,11 +211,17 @@ TB_HD int bpe_word(const DevBpe& T, const uint8_t* w, int L, BpeArr c, BpeArr r)
 // lookup of symbol i and its successor ((rank << 32 | merged id), ~0 = no merge), so a merge needs
 // only the two lookups of its new neighbours. Sequential (host); k_bpe_long runs the same merges
 // with the minimum search spread over a wave.
+template <class P = BpeGpt2>
 TB_HD int bpe_word_long(const DevBpe& T, const uint8_t* w, int L, uint32_t* c, uint64_t* v, int32_t* nx,
-                        int32_t* pv) {
-  if (L <= 1) return L;
+                        int32_t* pv, int lead = 0) {
+  if constexpr (P::kByteSymbols) {
+    if (L <= 1) return L;
+    for (int i = 0; i < L; ++i) c[i] = T.byte_id[w[i]];
+  } else {
+    L = P::symbols(T, w, L, lead, BpeArr{c, 1});  // (at most L + lead of them)
+    if (L <= 1) return L;
+  }
   for (int i = 0; i < L; ++i) {
-    c[i] = T.byte_id[w[i]];
     nx[i] = i + 1;
     pv[i] = i - 1;
   }
@@ -403,7 +435,7 @@ TB_HD int64_t bpe_first_start(const DevBpe& T, const uint8_t* b, int64_t n, int6
 // (first_start) and where its last one ends (range_end: the range's own end when token starts are
 // local, else the next range's first start), the sequential rule (next_token), the whole-piece
 // vocabulary lookup of ignore_merges (whole) and the added-token scan (has_added).
-struct BpeGpt2 {
+struct BpeGpt2 : BpeByteLevel {
   static constexpr bool kSyncSplit = false;
   static TB_HD int64_t first_start(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0) {
     return bpe_first_start(T, b, n, s0);
@@ -419,7 +451,8 @@ struct BpeGpt2 {
 };
 
 // Tokens (after merges) of the pre-tokens that start in [s, stop), s and stop token starts (or n);
-// a pre-token [s, e) over kBpeMaxWord bytes is handed to on_long(s, e) (its tokens, or < 0: fail).
+// a pre-token [s, e) over kBpeMaxWord bytes (with the policy's lead symbols) is handed to
+// on_long(s, e) (its tokens, or < 0: fail).
 // -1: count the document on the host (invalid UTF-8, or on_long failed).
 struct BpeNoLong {
   TB_HD int64_t operator()(int64_t, int64_t) const { return -1; }
@@ -433,7 +466,8 @@ TB_HD int64_t bpe_count_span(const DevBpe& T, const uint8_t* b, int64_t n, int64
   while (s < n && s < stop) {
     const int64_t e = P::next_token(T, b, n, s);
     if (e <= s) return -1;
-    if (e - s > kBpeMaxWord) {
+    const int lead = P::lead(T, b, n, s);
+    if (e - s + lead > kBpeMaxWord) {
       if (P::whole(T, b + s, e - s)) {
         total += kMerge ? 1 : 0;
       } else {
@@ -442,7 +476,7 @@ TB_HD int64_t bpe_count_span(const DevBpe& T, const uint8_t* b, int64_t n, int64
         total += k;
       }
     } else if (kMerge) {
-      total += P::whole(T, b + s, e - s) ? 1 : bpe_word(T, b + s, (int)(e - s), c, r);
+      total += P::whole(T, b + s, e - s) ? 1 : bpe_word<P>(T, b + s, (int)(e - s), c, r, lead);
     }
     s = e;
   }

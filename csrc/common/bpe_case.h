@@ -184,7 +184,7 @@ TB_HD int64_t bpe_case_sync(const DevBpe& T, const uint8_t* b, int64_t n, int64_
   return n;
 }
 
-struct BpeCase {
+struct BpeCase : BpeByteLevel {
   static constexpr bool kSyncSplit = true;
   static TB_HD int64_t first_start(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0) {
     return bpe_case_sync(T, b, n, s0);

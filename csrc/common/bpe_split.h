@@ -170,7 +170,7 @@ TB_HD bool bpe_split_has_added(const DevBpe& T, const uint8_t* b, int64_t n, int
   return false;
 }
 
-struct BpeSplit {
+struct BpeSplit : BpeByteLevel {
   static constexpr bool kSyncSplit = true;
   static TB_HD int64_t first_start(const DevBpe& T, const uint8_t* b, int64_t n, int64_t s0) {
     return bpe_split_sync(T, b, n, s0);

@@ -20,10 +20,14 @@
 // code points of its byte range, and a document that fails it goes to the host; the check is a
 // compile-time parameter of the body, so the other kernels carry none of it. k_bpe_case_count /
 // k_bpe_case_count_nfc / k_bpe_case_long are the instantiation for the case-aware patterns of
-// o200k_base and Tekken (csrc/common/bpe_case.h).
+// o200k_base and Tekken (csrc/common/bpe_case.h). k_bpe_sp_count / k_bpe_sp_long are the one for the
+// character-level BPE of the SentencePiece conversions (csrc/common/bpe_sp.h: Llama-2, Mistral,
+// Gemma): chunk starts are local, as GPT-2's, and the policy supplies a chunk's initial symbols
+// (code points looked up through the cache, <0xNN> ids for the others, the prepended U+2581).
 #include <hip/hip_runtime.h>
 
 #include "../common/bpe_case.h"
+#include "../common/bpe_sp.h"
 
 using namespace tb;
 
@@ -149,6 +153,14 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_case_count_nfc(DevBpe T, cons
   bpe_count_body<BpeCase, true>(T, text, off, n_dev, n_max, counts);
 }
 
+// k_bpe_count for the SentencePiece-style character-level BPE (T.sp_flags: the layout)
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_sp_count(DevBpe T, const uint8_t* __restrict__ text,
+                                                            const int64_t* __restrict__ off,
+                                                            const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                            int32_t* __restrict__ counts) {
+  bpe_count_body<BpeSp>(T, text, off, n_dev, n_max, counts);
+}
+
 constexpr int kBpeLongList = 32;  // long pre-tokens of one document counted on the device
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t x) {
@@ -159,20 +171,73 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t x) {
   return x;
 }
 
-// bpe_word_long (csrc/common/bpe.h) by one wave: the same linked-list merges, the search for the
-// leftmost lowest-rank pair spread over the lanes; lane 0 applies each merge
-__device__ int bpe_word_long_wave(const DevBpe& T, const uint8_t* w, int L, uint32_t* c, uint64_t* v, int16_t* nx,
-                                  int16_t* pv, int lane) {
-  if (L <= 1) return L;
+// The initial symbols of a BpeSp chunk (csrc/common/bpe_sp.h) for bpe_word_long_wave, the lanes
+// taking code points side by side: the symbol of the code point at byte i sits at slot i + lead
+// (slot 0: the prepended U+2581), linked to the slot after its last byte; the slots of its other
+// bytes are dead (nx = -1, no pair) unless it falls back to one <0xNN> symbol per byte. Returns
+// the number of symbols (the same in every lane); Lt = L + lead slots are in use.
+__device__ int bpe_sp_symbols_wave(const DevBpe& T, const uint8_t* w, int L, int lead, uint32_t* c, uint64_t* v,
+                                   int16_t* nx, int16_t* pv, int lane) {
+  const int Lt = L + lead;
+  int cnt = 0;
+  if (lane == 0) {
+    pv[0] = -1;
+    if (lead) {
+      c[0] = T.sp_id;
+      nx[0] = 1;
+      cnt = 1;
+    }
+  }
   for (int i = lane; i < L; i += 64) {
-    c[i] = T.byte_id[w[i]];
-    nx[i] = (int16_t)(i + 1);
-    pv[i] = (int16_t)(i - 1);
+    if ((w[i] & 0xC0) == 0x80) continue;  // (the chunk is valid UTF-8: its code point's lane writes this slot)
+    int l = 1;
+    const int32_t cp = bpe_decode(w, i, L, &l);
+    const uint32_t id = cp < 0 ? kBpeSpNone : bpe_sp_symbol(T, (uint32_t)cp);
+    const int q = i + lead;
+    if (id != kBpeSpNone) {
+      c[q] = id;
+      nx[q] = (int16_t)(q + l);
+      for (int j = 1; j < l; ++j) nx[q + j] = -1;
+      ++cnt;
+    } else {
+      for (int j = 0; j < l; ++j) {
+        c[q + j] = T.byte_id[w[i + j]];
+        nx[q + j] = (int16_t)(q + j + 1);
+      }
+      cnt += l;
+    }
   }
   __syncthreads();
-  for (int i = lane; i < L; i += 64) v[i] = i + 1 < L ? bpe_lookup(T, c[i], c[i + 1]) : ~0ull;
+  for (int i = lane; i < Lt; i += 64) {
+    const int j = nx[i];
+    if (j >= 0 && j < Lt) pv[j] = (int16_t)i;  // (every live slot but the first has one predecessor)
+    v[i] = (j >= 0 && j < Lt) ? bpe_lookup(T, c[i], c[j]) : ~0ull;
+  }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, kBpeLanes);
+  return cnt;
+}
+
+// bpe_word_long (csrc/common/bpe.h) by one wave: the same linked-list merges, the search for the
+// leftmost lowest-rank pair spread over the lanes; lane 0 applies each merge
+template <class P>
+__device__ int bpe_word_long_wave(const DevBpe& T, const uint8_t* w, int L, int lead, uint32_t* c, uint64_t* v,
+                                  int16_t* nx, int16_t* pv, int lane) {
+  int m;
+  if constexpr (P::kByteSymbols) {
+    if (L <= 1) return L;
+    for (int i = lane; i < L; i += 64) {
+      c[i] = T.byte_id[w[i]];
+      nx[i] = (int16_t)(i + 1);
+      pv[i] = (int16_t)(i - 1);
+    }
+    __syncthreads();
+    for (int i = lane; i < L; i += 64) v[i] = i + 1 < L ? bpe_lookup(T, c[i], c[i + 1]) : ~0ull;
+    m = L;
+  } else {
+    m = bpe_sp_symbols_wave(T, w, L, lead, c, v, nx, pv, lane);
+    L += lead;
+  }
   __syncthreads();
-  int m = L;
   while (m > 1) {
     uint64_t best = ~0ull;
     for (int i = lane; i < L; i += 64) {
@@ -232,7 +297,7 @@ __device__ __forceinline__ void bpe_long_body(const DevBpe& T, const uint8_t* __
     if (s0 < len) {
       const int64_t x = lane_count<false, P>(T, b, len, lo, hi, BpeArr{nullptr, 0}, BpeArr{nullptr, 0},
                                              [&](int64_t a, int64_t e) -> int64_t {
-                                          if (e - a > kBpeMaxLong) return -1;
+                                          if (e - a + P::lead(T, b, len, a) > kBpeMaxLong) return -1;
                                           const uint32_t q = atomicAdd(&nlong, 1u);
                                           if (q >= (uint32_t)kBpeLongList) return -1;
                                           ls[q] = a;
@@ -246,7 +311,7 @@ __device__ __forceinline__ void bpe_long_body(const DevBpe& T, const uint8_t* __
     __syncthreads();
     const uint32_t nl = nlong < (uint32_t)kBpeLongList ? nlong : (uint32_t)kBpeLongList;
     for (uint32_t q = 0; q < nl && !any_bad; ++q)
-      cnt += bpe_word_long_wave(T, b + ls[q], (int)(le[q] - ls[q]), lc, lv, lnx, lpv, t);
+      cnt += bpe_word_long_wave<P>(T, b + ls[q], (int)(le[q] - ls[q]), P::lead(T, b, len, ls[q]), lc, lv, lnx, lpv, t);
     if (t == 0) counts[k] = (any_bad || cnt > 0x7FFFFFFF) ? kBpeHost : (int32_t)cnt;
     __syncthreads();
   }
@@ -276,6 +341,14 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_case_long(DevBpe T, const uin
   bpe_long_body<BpeCase>(T, text, off, n_dev, n_max, counts);
 }
 
+// k_bpe_long for the SentencePiece-style character-level BPE
+__global__ __launch_bounds__(kBpeLanes) void k_bpe_sp_long(DevBpe T, const uint8_t* __restrict__ text,
+                                                           const int64_t* __restrict__ off,
+                                                           const int64_t* __restrict__ n_dev, int32_t n_max,
+                                                           int32_t* __restrict__ counts) {
+  bpe_long_body<BpeSp>(T, text, off, n_dev, n_max, counts);
+}
+
 }  // namespace
 
 // counts[k] for documents k < min(*n_dev, n_max) (n_dev may be null): text + off[k] .. off[k + 1]
@@ -283,7 +356,11 @@ extern "C" int tb_bpe_count(hipStream_t stream, const DevBpe* T, const uint8_t* 
                             const int64_t* n_dev, int32_t n_max, int32_t* counts) {
   if (n_max <= 0) return 0;
   if (T == nullptr || T->n_added < 0) return (int)hipErrorInvalidValue;
-  const bool split = bpe_kind_split(T->kind), cased = bpe_kind_case(T->kind);
+  const bool sp = T->kind == kBpeSp, cased = bpe_kind_case(T->kind);
+  const bool split = bpe_kind_mem_added(T->kind);  // (sp: its added tokens are the split family's)
+  if (sp && (T->ignore_merges || T->nfc || T->sp_ascii == nullptr || T->sp_cp == nullptr || T->byte_id == nullptr ||
+             !bpe_sp_flags_valid(T->sp_flags)))
+    return (int)hipErrorInvalidValue;
   if (split ? (T->n_added > kBpeSplitMaxAdded || (T->n_added && (T->aoff == nullptr || T->added == nullptr)) ||
                (T->ignore_merges && (T->vslots == nullptr || T->vpool == nullptr || T->vlongest < 1)))
             : (T->kind != kBpeGpt2 || T->n_added > kBpeMaxAdded))
@@ -301,6 +378,9 @@ extern "C" int tb_bpe_count(hipStream_t stream, const DevBpe* T, const uint8_t* 
       hipLaunchKernelGGL(k_bpe_case_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
     hipLaunchKernelGGL(k_bpe_case_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,
                        counts);
+  } else if (sp) {
+    hipLaunchKernelGGL(k_bpe_sp_count, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
+    hipLaunchKernelGGL(k_bpe_sp_long, dim3(grid_long), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max, counts);
   } else if (split) {
     if (T->nfc)
       hipLaunchKernelGGL(k_bpe_split_count_nfc, dim3(grid), dim3(kBpeLanes), 0, stream, *T, text, off, n_dev, n_max,

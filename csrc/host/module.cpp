@@ -14,6 +14,7 @@
 #include "../common/bpe.h"
 #include "../common/bpe_split.h"
 #include "../common/bpe_case.h"
+#include "../common/bpe_sp.h"
 #include "../common/bpe_classes.inc"
 #include "../common/nfc_qc.inc"
 #include "../common/bpe_case_classes.inc"
@@ -369,18 +370,28 @@ PYBIND11_MODULE(_tbhost, m) {
                         py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
                         int nthreads, int64_t chunk, int kind, bool ignore_merges,
                         py::array_t<uint64_t, py::array::c_style> vslots, uint32_t vmask,
-                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest, bool nfc) {
-    // host emulation of k_bpe_count / k_bpe_split_count (kind: BpeKind): per document the token
+                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest, bool nfc,
+                        py::array_t<uint32_t, py::array::c_style> sp_ascii,
+                        py::array_t<uint64_t, py::array::c_style> sp_cp, uint32_t sp_mask, uint32_t sp_id,
+                        int32_t sp_flags) {
+    // host emulation of k_bpe_count / k_bpe_split_count / k_bpe_sp_count (kind: BpeKind): per document the token
     // count, or kBpeHost. chunk > 0: the wave split — the pre-tokens starting in each chunk-byte
     // range counted independently (bpe_count_range), as the kernel's lanes do. nfc: behind the NFC
     // gate (bpe_nfc_range, per range in the chunk mode), as k_bpe_split_count_nfc
-    const bool split = bpe_kind_split(kind);
+    const bool sp = kind == kBpeSp, split = bpe_kind_split(kind) || sp;  // (split: added tokens in memory)
     if (byte_id.size() != 256 || (size_t)keys.size() != (size_t)mask + 1 || vals.size() != keys.size() ||
         (!split && kind != kBpeGpt2) || added_off.size() > (size_t)(split ? kBpeSplitMaxAdded : kBpeMaxAdded) + 1 ||
         (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size())) ||
         !std::is_sorted(added_off.begin(), added_off.end()) || (ignore_merges && !split) || (nfc && !split) ||
-        (ignore_merges && ((size_t)vslots.size() != 2 * ((size_t)vmask + 1) || vlongest < 1)))
+        (ignore_merges && ((size_t)vslots.size() != 2 * ((size_t)vmask + 1) || vlongest < 1)) ||
+        (sp && (ignore_merges || nfc || sp_ascii.size() != 128 || (size_t)sp_cp.size() != (size_t)sp_mask + 1 ||
+                !bpe_sp_flags_valid(sp_flags))))
       throw std::invalid_argument("bpe_count: operand shapes");
+    if (sp) {  // a free slot ends every probe
+      bool free_slot = false;
+      for (size_t i = 0; i <= sp_mask; ++i) free_slot = free_slot || sp_cp.data()[i] == kBpeSpEmpty;
+      if (!free_slot) throw std::invalid_argument("bpe_count: code point table");
+    }
     if (ignore_merges)  // every listed entry lies in the pool
       for (size_t i = 0; i <= vmask; ++i) {
         const uint64_t v = vslots.data()[2 * i + 1];
@@ -416,6 +427,11 @@ PYBIND11_MODULE(_tbhost, m) {
     T.nfc1 = TB_NFC_QC_STAGE1;
     T.nfc2 = TB_NFC_QC_STAGE2;
     T.nfc = nfc;
+    T.sp_ascii = sp_ascii.data();
+    T.sp_cp = sp_cp.data();
+    T.sp_mask = sp_mask;
+    T.sp_id = sp_id;
+    T.sp_flags = sp_flags;
     const uint8_t* d = data.data();
     const int64_t* o = off.data();
     auto run = [&](auto policy) {
@@ -430,15 +446,17 @@ PYBIND11_MODULE(_tbhost, m) {
           std::vector<uint64_t> lv(kBpeMaxLong);
           std::vector<int32_t> lnx(kBpeMaxLong), lpv(kBpeMaxLong);
           const uint8_t* b = nullptr;
+          int64_t n = 0;
           // pre-tokens over kBpeMaxWord bytes: merged over arrays of their own length (as
           // k_bpe_long does), up to kBpeMaxLong bytes
           auto on_long = [&](int64_t s, int64_t e) -> int64_t {
-            if (e - s > kBpeMaxLong) return -1;
-            return bpe_word_long(T, b + s, (int)(e - s), lc.data(), lv.data(), lnx.data(), lpv.data());
+            const int lead = P::lead(T, b, n, s);
+            if (e - s + lead > kBpeMaxLong) return -1;
+            return bpe_word_long<P>(T, b + s, (int)(e - s), lc.data(), lv.data(), lnx.data(), lpv.data(), lead);
           };
           for (int64_t k = t; k < nd; k += nt) {
             b = d + o[k];
-            const int64_t n = o[k + 1] - o[k];
+            n = o[k + 1] - o[k];
             if (chunk <= 0) {
               out[k] = bpe_count_doc<P>(T, b, n, BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
               continue;
@@ -461,6 +479,7 @@ PYBIND11_MODULE(_tbhost, m) {
       for (auto& x : th) x.join();
     };
     if (bpe_kind_case(kind)) run(BpeCase{});
+    else if (sp) run(BpeSp{});
     else if (split) run(BpeSplit{});
     else run(BpeGpt2{});
     return to_numpy(std::move(out));
@@ -469,7 +488,22 @@ PYBIND11_MODULE(_tbhost, m) {
         py::arg("kind") = 0, py::arg("ignore_merges") = false,
         py::arg("vslots") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("vmask") = 0,
         py::arg("vpool") = py::array_t<uint8_t, py::array::c_style>(0), py::arg("vlongest") = 0,
-        py::arg("nfc") = false);
+        py::arg("nfc") = false, py::arg("sp_ascii") = py::array_t<uint32_t, py::array::c_style>(0),
+        py::arg("sp_cp") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("sp_mask") = 0, py::arg("sp_id") = 0,
+        py::arg("sp_flags") = 0);
+  m.def("bpe_sp_build_table", [](py::array_t<uint32_t, py::array::c_style> cps, py::array_t<uint32_t, py::array::c_style> ids) {
+    // DevBpe::sp_cp (csrc/common/bpe_sp.h): code point -> id of the single-character vocabulary
+    // entries above ASCII
+    const size_t n = (size_t)cps.size();
+    if ((size_t)ids.size() != n) throw std::invalid_argument("bpe_sp_build_table: operand shapes");
+    for (size_t i = 0; i < n; ++i)
+      if (cps.data()[i] < 128 || cps.data()[i] > 0x10FFFF) throw std::invalid_argument("bpe_sp_build_table: code point");
+    size_t cap = 16;
+    while (cap < 2 * n) cap <<= 1;
+    std::vector<uint64_t> slots(cap);
+    bpe_sp_fill(cps.data(), ids.data(), n, slots.data(), (uint32_t)(cap - 1));
+    return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)(cap - 1));
+  });
   m.def("nfc_qc", []() {
     // the NFC gate's two-stage table (csrc/common/nfc_qc.inc)
     std::vector<uint8_t> t1(TB_NFC_QC_STAGE1, TB_NFC_QC_STAGE1 + sizeof(TB_NFC_QC_STAGE1));

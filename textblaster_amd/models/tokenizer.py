@@ -23,6 +23,10 @@ BertPreTokenizer, the BERT family) get a :class:`WordPieceSpec` instead (:meth:`
 open-addressed hash table over a byte pool (csrc/common/wordpiece.h, k_wp_count). With ``lowercase``
 or ``strip_accents`` the device path counts with :meth:`TokenCounterModel.wordpiece_fold_spec`, which
 names the fold tables of the tokenizer's mode (csrc/common/wp_fold.inc, k_wp_count_fold).
+The SentencePiece-converted character-level BPE files with ``byte_fallback`` (Llama-2, Mistral, Gemma:
+normalizer Prepend + Replace(" ", "▁") and no pre-tokenizer, or a Metaspace pre-tokenizer) get a
+:class:`BpeSpec` of kind ``BPE_SP`` (csrc/common/bpe_sp.h, k_bpe_sp_count): the ids of the
+single-character entries, of the 256 ``<0xNN>`` tokens and of ``▁``, and the prepend and split rules.
 """
 from __future__ import annotations
 
@@ -75,7 +79,8 @@ MAX_ADDED = 8  # csrc/common/bpe.h kBpeMaxAdded
 
 @dataclasses.dataclass
 class BpeSpec:
-    """Device tables of a byte-level BPE tokenizer (csrc/common/bpe.h DevBpe)."""
+    """Device tables of a byte-level, or SentencePiece-style character-level, BPE tokenizer
+    (csrc/common/bpe.h DevBpe)."""
     byte_id: np.ndarray    # uint32 [256]
     keys: np.ndarray       # uint64 [mask + 1]
     vals: np.ndarray       # uint64 [mask + 1]
@@ -84,7 +89,7 @@ class BpeSpec:
     added_off: List[int]   # [n_added + 1]
     post_add: int          # tokens the post-processor adds
     # the split-regex family (csrc/common/bpe_split.h); GPT-2 keeps the defaults
-    kind: int = 0                          # BPE_GPT2 / BPE_SPLIT_A / BPE_SPLIT_B / BPE_CASE_C / BPE_CASE_D
+    kind: int = 0                          # BPE_GPT2 / BPE_SPLIT_A / BPE_SPLIT_B / BPE_CASE_C / BPE_CASE_D / BPE_SP
     ignore_merges: bool = False
     vslots: Optional[np.ndarray] = None    # uint64 [2 * (vmask + 1)]: the vocabulary's raw bytes, WpSlot pairs
     vmask: int = 0
@@ -92,9 +97,23 @@ class BpeSpec:
     vlongest: int = 0                      # bytes of the longest entry
     added_mask: Optional[np.ndarray] = None  # uint64 [4]: first bytes of the added tokens
     nfc: bool = False                      # the normalizer is NFC: documents it may change come back -2
+    # the SentencePiece-style family (kind BPE_SP, csrc/common/bpe_sp.h): byte_id holds the ids of <0xNN>
+    sp_prepend: int = 0                    # SP_PREPEND_*: a U+2581 in front of the text
+    sp_split: bool = False                 # a chunk starts at every space (Metaspace split), not only after a word
+    sp_ascii: Optional[np.ndarray] = None  # uint32 [128]: id of each ASCII character, 0xFFFFFFFF = no entry
+    sp_cp: Optional[np.ndarray] = None     # uint64 [sp_mask + 1]: (code point << 32 | id) of the other characters
+    sp_mask: int = 0
+    sp_id: int = 0                         # id of U+2581
+
+    @property
+    def sp_flags(self) -> int:
+        return self.sp_prepend | (4 if self.sp_split else 0)  # bpe_sp.h BpeSpFlags
 
 
 BPE_GPT2, BPE_SPLIT_A, BPE_SPLIT_B, BPE_CASE_C, BPE_CASE_D = 0, 1, 2, 3, 4  # csrc/common/bpe.h BpeKind
+BPE_SP = 5  # SentencePiece-style character-level BPE with byte_fallback (csrc/common/bpe_sp.h)
+SP_SPACE = "▁"  # "▁": what these tokenizers write for U+0020
+SP_PREPEND_NONE, SP_PREPEND_ALWAYS, SP_PREPEND_UNLESS_SPACE = 0, 1, 2  # bpe_sp.h kBpeSpPrepend*
 SPLIT_MAX_ADDED, SPLIT_MAX_ADDED_BYTES = 1024, 65536  # kBpeSplitMaxAdded, kBpeSplitMaxAddedBytes
 # the Split patterns counted on the device: Llama-3 / cl100k_base, and the Qwen2 family
 SPLIT_PATTERN_A = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
@@ -159,6 +178,103 @@ def _post_add(pp) -> Optional[int]:
     return None
 
 
+def _sp_layout(tj: dict):
+    """(SP_PREPEND_*, split) when normalizer and pre-tokenizer are one of the two layouts of the
+    SentencePiece-style family, else None: L = no pre-tokenizer behind Replace(" ", "▁") or
+    Sequence[Prepend("▁"), Replace(" ", "▁")]; M = no normalizer, Metaspace("▁", prepend_scheme, split)."""
+    nz, pt = tj.get("normalizer"), tj.get("pre_tokenizer")
+    replace = {"type": "Replace", "pattern": {"String": " "}, "content": SP_SPACE}
+    if pt is None:
+        if nz == replace:
+            return SP_PREPEND_NONE, False
+        if nz == {"type": "Sequence", "normalizers": [{"type": "Prepend", "prepend": SP_SPACE}, replace]}:
+            return SP_PREPEND_ALWAYS, False
+        return None
+    if nz is not None or not isinstance(pt, dict) or set(pt) != {"type", "replacement", "prepend_scheme", "split"}:
+        return None
+    if pt["type"] != "Metaspace" or pt["replacement"] != SP_SPACE or not isinstance(pt["split"], bool):
+        return None
+    # "first" is "always" here: a document with an added token's text, the only kind the library
+    # cuts into sections, goes to the host
+    prepend = {"always": SP_PREPEND_UNLESS_SPACE, "first": SP_PREPEND_UNLESS_SPACE,
+               "never": SP_PREPEND_NONE}.get(pt["prepend_scheme"])
+    return None if prepend is None else (prepend, pt["split"])
+
+
+def _merge_pairs(m: dict, vocab: dict):
+    """The merges as (left id, right id, rank, merged id) lists and their string pairs, None when an
+    entry is malformed or names a string that is not in the vocabulary."""
+    a, b, rank, nid, pairs = [], [], [], [], []
+    for i, mg in enumerate(m.get("merges") or []):
+        parts = mg.split(" ") if isinstance(mg, str) else mg
+        if len(parts) != 2:
+            return None
+        x, y = parts
+        if x not in vocab or y not in vocab or (x + y) not in vocab:
+            return None
+        a.append(vocab[x])
+        b.append(vocab[y])
+        rank.append(i)
+        nid.append(vocab[x + y])
+        pairs.append((x, y))
+    return a, b, rank, nid, pairs
+
+
+def _build_sp_spec(tj: dict, prepend: int, split: bool) -> Optional[BpeSpec]:
+    """BpeSpec of kind BPE_SP for a character-level BPE with byte_fallback in layout L or M (see
+    :func:`_sp_layout`), None when the device counter would not reproduce it: all 256 ``<0xNN>``
+    tokens and ``▁`` must be in the vocabulary (``unk`` can then never appear), no ignore_merges,
+    and without Metaspace's split no merge may join a piece that ends in another character than
+    ``▁`` to one that starts with ``▁`` (then the merges of the whole text are those of its
+    chunks ``▁* [^▁]*``, which is what the counter merges)."""
+    from .. import native
+
+    m = tj["model"]
+    vocab = m.get("vocab") or {}
+    if m.get("ignore_merges") or not isinstance(vocab, dict) or SP_SPACE not in vocab:
+        return None
+    byte_tokens = [f"<0x{b:02X}>" for b in range(256)]
+    if any(t not in vocab for t in byte_tokens):
+        return None
+    post = _post_add(tj.get("post_processor"))
+    mg = _merge_pairs(m, vocab)
+    if post is None or mg is None:
+        return None
+    a, b, rank, nid, pairs = mg
+    if not split and any(x and y and x[-1] != SP_SPACE and y[0] == SP_SPACE for x, y in pairs):
+        return None
+    toks = [t for t in tj.get("added_tokens") or [] if t.get("content")]
+    # matched on normalised text: the same statement about the raw text only without a space in it
+    if any(t.get("normalized") and (" " in t["content"] or SP_SPACE in t["content"]) for t in toks):
+        return None
+    added = [t["content"].encode("utf-8") for t in toks]
+    off = [0]
+    for t in added:
+        off.append(off[-1] + len(t))
+    if len(added) > SPLIT_MAX_ADDED or off[-1] > SPLIT_MAX_ADDED_BYTES:
+        return None
+    h = native.host()
+    u32 = lambda v: np.array(v, dtype=np.uint32)  # noqa: E731
+    keys, vals, mask = h.bpe_build_table(u32(a), u32(b), u32(rank), u32(nid))
+    sp_ascii = np.full(128, 0xFFFFFFFF, dtype=np.uint32)
+    cps, ids = [], []
+    for s, i in vocab.items():
+        if len(s) == 1:
+            if ord(s) < 128:
+                sp_ascii[ord(s)] = i
+            else:
+                cps.append(ord(s))
+                ids.append(i)
+    sp_cp, sp_mask = h.bpe_sp_build_table(u32(cps), u32(ids))
+    spec = BpeSpec(u32([vocab[t] for t in byte_tokens]), keys, vals, int(mask),
+                   np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(), off if added else [], post)
+    spec.kind = BPE_SP
+    spec.added_mask = h.bpe_added_mask(spec.added, spec.added_off)
+    spec.sp_prepend, spec.sp_split = prepend, split
+    spec.sp_ascii, spec.sp_cp, spec.sp_mask, spec.sp_id = sp_ascii, sp_cp, int(sp_mask), int(vocab[SP_SPACE])
+    return spec
+
+
 def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
     """BpeSpec of a parsed tokenizer.json, or None when the tokenizer is not a byte-level BPE the
     device counter reproduces exactly: plain BPE merges, no truncation / padding, a known
@@ -170,7 +286,11 @@ def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
     A tokenizer with a normalizer has no spec, unless ``nfc`` is set (as :meth:`TokenCounterModel.bpe_spec`
     does): then a split-regex tokenizer whose normalizer is exactly ``{"type": "NFC"}`` and that has
     no added token matched on normalised text gets a spec with ``nfc`` on, whose counter returns -2
-    for every document it cannot prove NFC leaves unchanged."""
+    for every document it cannot prove NFC leaves unchanged.
+
+    A character-level BPE with ``byte_fallback`` in one of the SentencePiece-style layouts (Llama-2,
+    Mistral, Gemma: :func:`_sp_layout`) gets a spec of kind BPE_SP under the conditions of
+    :func:`_build_sp_spec`."""
     from .. import native
 
     m = tj.get("model") or {}
@@ -179,6 +299,10 @@ def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
         return None
     if tj.get("truncation") is not None or tj.get("padding") is not None:
         return None
+    if m.get("byte_fallback"):
+        layout = _sp_layout(tj)
+        if layout is not None:
+            return _build_sp_spec(tj, *layout)
     pt = tj.get("pre_tokenizer")
     kind = _split_kind(pt)
     nz = tj.get("normalizer")
@@ -204,21 +328,10 @@ def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
     if any(ch not in vocab for ch in b2u):
         return None
     byte_id = np.array([vocab[ch] for ch in b2u], dtype=np.uint32)
-    a, b, rank, nid = [], [], [], []
-    for i, mg in enumerate(m.get("merges") or []):
-        if isinstance(mg, str):
-            parts = mg.split(" ")
-            if len(parts) != 2:
-                return None
-        else:
-            parts = mg
-        x, y = parts
-        if x not in vocab or y not in vocab or (x + y) not in vocab:
-            return None
-        a.append(vocab[x])
-        b.append(vocab[y])
-        rank.append(i)
-        nid.append(vocab[x + y])
+    mg = _merge_pairs(m, vocab)
+    if mg is None:
+        return None
+    a, b, rank, nid, _ = mg
     u32 = lambda v: np.array(v, dtype=np.uint32)  # noqa: E731
     keys, vals, mask = native.host().bpe_build_table(u32(a), u32(b), u32(rank), u32(nid))
     added = [t["content"].encode("utf-8") for t in tj.get("added_tokens") or [] if t.get("content")]
@@ -383,7 +496,7 @@ class TokenCounterModel:
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
         """Token counts of packed UTF-8 documents with the native counter of whichever spec the
         tokenizer has (host emulation of k_bpe_count / k_wp_count); documents it returns -2 for
-        (added-token text, invalid UTF-8, BPE pre-tokens over 2048 bytes, text that an NFC normalizer
+        (added-token text, invalid UTF-8, BPE pre-tokens or SentencePiece-style chunks over 2048 bytes, text that an NFC normalizer
         may change, WordPiece text with a code point whose place NFD may change under strip_accents) are counted by ``tokenizers``."""
         from .. import native
 
@@ -412,6 +525,10 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
         return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
                            nthreads, chunk)
     none64, none8 = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint8)
+    if sp.kind == BPE_SP:
+        return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
+                           nthreads, chunk, sp.kind, sp_ascii=sp.sp_ascii, sp_cp=sp.sp_cp, sp_mask=sp.sp_mask,
+                           sp_id=sp.sp_id, sp_flags=sp.sp_flags)
     return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
                        nthreads, chunk, sp.kind, sp.ignore_merges, none64 if sp.vslots is None else sp.vslots,
                        sp.vmask, none8 if sp.vpool is None else sp.vpool, sp.vlongest, sp.nfc)
@@ -514,6 +631,79 @@ def train_synthetic_split_bpe(path: str, vocab_size: int = 32000, pattern: str =
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f"{path}.{os.getpid()}.tmp"
     tok.save(tmp)
+    os.replace(tmp, path)
+    return path
+
+
+_SP_SPECIAL = ["<unk>", "<s>", "</s>"]
+_sp_trained: dict = {}  # (vocab_size, n_docs, seed) -> serialised tokenizer: the layouts share one training run
+
+
+def _train_sp_base(vocab_size: int, n_docs: int, seed: int) -> dict:
+    key = (vocab_size, n_docs, seed)
+    if key not in _sp_trained:
+        from tokenizers import Tokenizer, models, pre_tokenizers, trainers
+
+        from ..utils import synth
+
+        texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
+        tok = Tokenizer(models.BPE(unk_token="<unk>"))
+        tok.pre_tokenizer = pre_tokenizers.Metaspace(replacement=SP_SPACE, prepend_scheme="always", split=True)
+        tr = trainers.BpeTrainer(vocab_size=vocab_size, show_progress=False,
+                                 special_tokens=_SP_SPECIAL + [f"<0x{b:02X}>" for b in range(256)])
+        tok.train_from_iterator(texts, tr)
+        _sp_trained[key] = tok.to_str()
+    return json.loads(_sp_trained[key])
+
+
+def train_synthetic_sp_bpe(path: str, vocab_size: int = 32000, layout: str = "L", prepend: bool = True,
+                           prepend_scheme: str = "first", split: bool = True, n_docs: int = 20000,
+                           seed: int = 1) -> str:
+    """Train a SentencePiece-style character-level BPE tokenizer on the synthetic Zipf corpus and
+    save it as ``path`` (kept if it already exists): trained behind Metaspace(split=true) with
+    ``<unk>``, ``<s>``, ``</s>`` and the 256 ``<0xNN>`` byte tokens in front of the vocabulary, then
+    written with ``byte_fallback`` and ``fuse_unk`` on, a template that puts ``<s>`` in front, and
+
+    * ``layout="L"`` (Llama-2, Mistral, Gemma): normalizer Sequence[Prepend("▁"), Replace(" ", "▁")]
+      (``prepend`` false: the Replace alone), no pre-tokenizer;
+    * ``layout="M"``: no normalizer, pre-tokenizer Metaspace("▁", ``prepend_scheme``, ``split``).
+
+    The stand-in for the files of those models, which cannot be downloaded here; the counts differ
+    from theirs, the work per byte is of the same kind."""
+    if os.path.isfile(path):
+        return path
+    if layout not in ("L", "M") or prepend_scheme not in ("always", "first", "never"):
+        raise ValueError("train_synthetic_sp_bpe: layout is L or M, prepend_scheme always, first or never")
+    from tokenizers import Tokenizer
+
+    tj = _train_sp_base(vocab_size, n_docs, seed)
+    # the byte tokens are plain vocabulary entries, as the SentencePiece conversions have them
+    tj["added_tokens"] = [t for t in tj["added_tokens"] if t["content"] in _SP_SPECIAL]
+    tj["model"].update(byte_fallback=True, fuse_unk=True, unk_token="<unk>", ignore_merges=False)
+    replace = {"type": "Replace", "pattern": {"String": " "}, "content": SP_SPACE}
+    if layout == "L":
+        tj["normalizer"] = ({"type": "Sequence", "normalizers": [{"type": "Prepend", "prepend": SP_SPACE}, replace]}
+                            if prepend else replace)
+        tj["pre_tokenizer"] = None
+    else:
+        tj["normalizer"] = None
+        tj["pre_tokenizer"] = {"type": "Metaspace", "replacement": SP_SPACE, "prepend_scheme": prepend_scheme,
+                               "split": split}
+    bos = tj["model"]["vocab"]["<s>"]
+    tj["post_processor"] = {
+        "type": "TemplateProcessing",
+        "single": [{"SpecialToken": {"id": "<s>", "type_id": 0}}, {"Sequence": {"id": "A", "type_id": 0}}],
+        "pair": [{"SpecialToken": {"id": "<s>", "type_id": 0}}, {"Sequence": {"id": "A", "type_id": 0}},
+                 {"SpecialToken": {"id": "<s>", "type_id": 1}}, {"Sequence": {"id": "B", "type_id": 1}}],
+        "special_tokens": {"<s>": {"id": "<s>", "ids": [bos], "tokens": ["<s>"]}}}
+    tj["decoder"] = {"type": "Sequence", "decoders": [
+        {"type": "Replace", "pattern": {"String": SP_SPACE}, "content": " "}, {"type": "ByteFallback"},
+        {"type": "Fuse"}]}
+    Tokenizer.from_str(json.dumps(tj))  # the library reads what was written
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    with open(tmp, "w", encoding="utf-8") as f:
+        json.dump(tj, f, ensure_ascii=False)
     os.replace(tmp, path)
     return path
 

@@ -164,7 +164,8 @@ class DevBpe(ctypes.Structure):
                 ("aoff", _P), ("vslots", _P), ("vpool", _P), ("nfc1", _P), ("nfc2", _P),
                 ("ccls1", _P), ("ccls2", _P),
                 ("amask", ctypes.c_uint64 * 4), ("vmask", _U32), ("vlongest", _I32), ("kind", _I32),
-                ("ignore_merges", _I32), ("nfc", _I32), ("pad_", _I32)]
+                ("ignore_merges", _I32), ("nfc", _I32), ("sp_flags", _I32),
+                ("sp_ascii", _P), ("sp_cp", _P), ("sp_mask", _U32), ("sp_id", _U32)]
 
 
 class BpeTables:
@@ -202,6 +203,14 @@ class BpeTables:
                 self.arrays += [hiprt.to_device(spec.vslots), hiprt.to_device(spec.vpool)]
                 st.vslots, st.vpool = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
                 st.vmask, st.vlongest, st.ignore_merges = spec.vmask, spec.vlongest, 1
+        if spec.kind == 5:
+            # the SentencePiece-style family (csrc/common/bpe_sp.h): the single-character entries' ids
+            if (spec.sp_ascii is None or len(spec.sp_ascii) != 128 or spec.sp_cp is None
+                    or len(spec.sp_cp) != spec.sp_mask + 1 or not (spec.sp_cp == np.uint64(2 ** 64 - 1)).any()):
+                raise DeviceError("bpe: code point tables")
+            self.arrays += [hiprt.to_device(spec.sp_ascii), hiprt.to_device(spec.sp_cp)]
+            st.sp_ascii, st.sp_cp = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
+            st.sp_mask, st.sp_id, st.sp_flags = spec.sp_mask, spec.sp_id, spec.sp_flags
         if spec.kind in (3, 4):
             # the case-aware patterns' class table (csrc/common/bpe_case_classes.inc)
             if case_tables is None:
@@ -507,7 +516,8 @@ class Kernels:
                          h.bpe_case_classes() if spec.kind in (3, 4) else None)
 
     def bpe_count(self, tabs: BpeTables, text, off, n_dev, n_max: int, counts):
-        """k_bpe_count + k_bpe_long, or for a split-regex spec k_bpe_split_count + k_bpe_split_long
+        """k_bpe_count + k_bpe_long, or for a split-regex spec k_bpe_split_count + k_bpe_split_long,
+        for a SentencePiece-style spec k_bpe_sp_count + k_bpe_sp_long
         (k_bpe_case_count + k_bpe_case_long for the case-aware patterns; the _nfc count kernels behind
         the NFC gate):
         token counts of documents k < min(n_dev[0], n_max) (csrc/hip/bpe.hip); ``n_dev``: optional

@@ -173,9 +173,10 @@ class Engine:
         self._bw_nolist = set()
         self.device_runner = None
         # trailing TokenCounter steps (after every filter) whose tokenizer is a byte-level BPE (GPT-2's
-        # ByteLevel regex, or the Llama-3 / cl100k_base / Qwen2 Split patterns) or a BERT-style
-        # WordPiece are counted by the device path on the kept outputs (k_bpe_count /
-        # k_bpe_split_count / k_wp_count); the others on the host
+        # ByteLevel regex, or the Llama-3 / cl100k_base / Qwen2 Split patterns), a SentencePiece-style
+        # character-level BPE (Llama-2 / Mistral / Gemma) or a BERT-style WordPiece are counted by the
+        # device path on the kept outputs (k_bpe_count / k_bpe_split_count / k_bpe_sp_count /
+        # k_wp_count); the others on the host
         from .device import trailing_token_counters
 
         self._trailing_tc = set(trailing_token_counters(self.plan))
