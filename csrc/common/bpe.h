@@ -2,7 +2,7 @@
 // ``tokenizer.encode(text, true).get_tokens().len()``) for GPT-2-style tokenizers: the ByteLevel
 // pre-tokenizer regex, then BPE merges per pre-token, plus the tokens the post-processor adds.
 // Shared by the HIP kernel (csrc/hip/bpe.hip: one lane per kept document, merge state in LDS)
-// and its host emulation (csrc/host/module.cpp bpe_count), which CPU tests pin to the
+// and its host emulation (csrc/host/tok_module.cpp bpe_count), which CPU tests pin to the
 // `tokenizers` library itself.
 //
 // Pre-tokenization. The regex ``'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|
@@ -101,6 +101,37 @@ struct DevBpe {
   uint32_t sp_mask;
   uint32_t sp_id;            // id of U+2581, which U+0020 is counted as too
 };
+
+// DevBpe::sp_flags (kBpeSp, csrc/common/bpe_sp.h; sp: U+2581, or the U+0020 it stands for)
+enum BpeSpFlags : int {
+  kBpeSpPrependAlways = 1,       // a U+2581 in front of every text that is not empty
+  kBpeSpPrependUnlessSpace = 2,  // ... unless it starts with sp
+  kBpeSpPrependMask = 3,
+  kBpeSpSplit = 4                // a chunk starts at every sp
+};
+
+// the flags of a layout: one prepend rule; a split only with Metaspace's rule or none
+TB_HD bool bpe_sp_flags_valid(int flags) {
+  return !(flags & ~(kBpeSpPrependMask | kBpeSpSplit)) && (flags & kBpeSpPrependMask) != kBpeSpPrependMask &&
+         flags != (kBpeSpPrependAlways | kBpeSpSplit);
+}
+
+// Can the counters of T's kind run on this block? The tables its family reads have addresses and
+// its flags go together (host: tb_bpe_count before it launches, bpe_fill_params before it returns).
+inline bool bpe_params_ok(const DevBpe& T) {
+  if (T.n_added < 0) return false;
+  const bool sp = T.kind == kBpeSp, cased = bpe_kind_case(T.kind);
+  const bool split = bpe_kind_mem_added(T.kind);  // (sp: its added tokens are the split family's)
+  if (sp && (T.ignore_merges || T.nfc || T.sp_ascii == nullptr || T.sp_cp == nullptr || T.byte_id == nullptr ||
+             !bpe_sp_flags_valid(T.sp_flags)))
+    return false;
+  if (split ? (T.n_added > kBpeSplitMaxAdded || (T.n_added && (T.aoff == nullptr || T.added == nullptr)) ||
+               (T.ignore_merges && (T.vslots == nullptr || T.vpool == nullptr || T.vlongest < 1)))
+            : (T.kind != kBpeGpt2 || T.n_added > kBpeMaxAdded))
+    return false;
+  if (T.nfc && (!split || T.nfc1 == nullptr || T.nfc2 == nullptr)) return false;
+  return !cased || (T.ccls1 != nullptr && T.ccls2 != nullptr);
+}
 
 TB_HD uint64_t bpe_hash(uint64_t k) {
   k ^= k >> 33;

@@ -2,7 +2,7 @@
 // counting loops of bpe.h, beside BpeSplit (bpe_split.h), with the same layout
 // Sequence[Split(Regex(P), Isolated), ByteLevel(use_regex=false)], ignore_merges and added tokens.
 // Shared by the HIP kernels (csrc/hip/bpe.hip k_bpe_case_count / k_bpe_case_long) and the host
-// emulation (csrc/host/module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
+// emulation (csrc/host/tok_module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
 //
 // Pattern C (o200k_base), with Up = [\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}], Lo = [\p{Ll}\p{Lm}\p{Lo}\p{M}]
 // and S = (?i:'s|'t|'re|'ve|'m|'ll|'d):

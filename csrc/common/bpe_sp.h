@@ -1,7 +1,7 @@
 // Character-level BPE token counting for the SentencePiece-converted tokenizers (Llama-2, Mistral
 // v0.1-0.3, TinyLlama, Phi-3, Gemma): the policy BpeSp of the counting loops of bpe.h.
 // Shared by the HIP kernels (csrc/hip/bpe.hip k_bpe_sp_count / k_bpe_sp_long) and the host
-// emulation (csrc/host/module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
+// emulation (csrc/host/tok_module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
 //
 // These files have no ByteLevel alphabet. The space is written U+2581, the model's symbols are code
 // points, and a code point that is no vocabulary entry becomes one <0xNN> token per UTF-8 byte
@@ -35,18 +35,7 @@ namespace tb {
 constexpr uint32_t kBpeSpNone = 0xFFFFFFFFu;   // sp_ascii: the code point is no vocabulary entry
 constexpr uint64_t kBpeSpEmpty = ~0ull;        // sp_cp: free slot
 constexpr uint32_t kBpeSpSpace = 0x2581;
-enum BpeSpFlags : int {
-  kBpeSpPrependAlways = 1,       // a U+2581 in front of every text that is not empty
-  kBpeSpPrependUnlessSpace = 2,  // ... unless it starts with sp
-  kBpeSpPrependMask = 3,
-  kBpeSpSplit = 4                // a chunk starts at every sp
-};
-
-// the flags of a layout: one prepend rule; a split only with Metaspace's rule or none
-TB_HD bool bpe_sp_flags_valid(int flags) {
-  return !(flags & ~(kBpeSpPrependMask | kBpeSpSplit)) && (flags & kBpeSpPrependMask) != kBpeSpPrependMask &&
-         flags != (kBpeSpPrependAlways | kBpeSpSplit);
-}
+// (BpeSpFlags and bpe_sp_flags_valid: bpe.h, next to the block they are a field of)
 
 TB_HD bool bpe_sp_is_space(int32_t c) { return c == ' ' || c == (int32_t)kBpeSpSpace; }
 

@@ -3,7 +3,7 @@
 // conversions, Qwen2; behind Qwen2's NFC normalizer the NFC gate of bpe.h decides per document): the
 // policy BpeSplit of the counting loops of bpe.h.
 // Shared by the HIP kernels (csrc/hip/bpe.hip k_bpe_split_count / k_bpe_split_long) and the host
-// emulation (csrc/host/module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
+// emulation (csrc/host/tok_module.cpp bpe_count), which CPU tests pin to the `tokenizers` library.
 //
 // Pattern A: (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}|
 //            ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+

@@ -2,7 +2,7 @@
 // ``tokenizer.encode(text, true).get_tokens().len()``) for tokenizers made of BertNormalizer +
 // BertPreTokenizer + a WordPiece model, plus the tokens the post-processor adds. Shared by the HIP
 // kernel (csrc/hip/wordpiece.hip: one wave per kept document, a byte range per lane) and its host
-// emulation (csrc/host/module.cpp wp_count), which CPU tests pin to the `tokenizers` library.
+// emulation (csrc/host/tok_module.cpp wp_count), which CPU tests pin to the `tokenizers` library.
 //
 // Words. Every code point has a class (wp_classes.inc, generated from the library): keep, drop
 // (removed, so its neighbours join), space, isolate (punctuation and CJK ideographs: a word of its
@@ -72,6 +72,13 @@ struct DevWp {
   int32_t n_added;
   int32_t added_off[kBpeMaxAdded + 1];
 };
+
+// Can the counters run on this block? (host: tb_wp_count before it launches, wp_fill_params before
+// it returns.) fold1 set selects the folding kernel, which reads all three fold tables.
+inline bool wp_params_ok(const DevWp& T) {
+  if (T.n_added < 0 || T.n_added > kBpeMaxAdded || T.longest < 1 || T.max_chars < 0) return false;
+  return T.fold1 == nullptr || (T.fold2 != nullptr && T.foldp != nullptr);
+}
 
 // hash state of a byte string: h(s + c) = h(s) * B + c + 1, h("") = 0
 TB_HD uint64_t wp_push(uint64_t h, uint32_t byte) { return h * kWpBase + byte + 1; }

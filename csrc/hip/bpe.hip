@@ -24,6 +24,10 @@
 // character-level BPE of the SentencePiece conversions (csrc/common/bpe_sp.h: Llama-2, Mistral,
 // Gemma): chunk starts are local, as GPT-2's, and the policy supplies a chunk's initial symbols
 // (code points looked up through the cache, <0xNN> ids for the others, the prepended U+2581).
+//
+// The parameter block DevBpe comes ready from the host module (csrc/host/tok_params.h
+// bpe_fill_params, the filler of the host emulation's block too, here with HBM addresses);
+// tb_bpe_count only asks bpe_params_ok (csrc/common/bpe.h) whether the kernels can run on it.
 #include <hip/hip_runtime.h>
 
 #include "../common/bpe_case.h"
@@ -355,18 +359,9 @@ __global__ __launch_bounds__(kBpeLanes) void k_bpe_sp_long(DevBpe T, const uint8
 extern "C" int tb_bpe_count(hipStream_t stream, const DevBpe* T, const uint8_t* text, const int64_t* off,
                             const int64_t* n_dev, int32_t n_max, int32_t* counts) {
   if (n_max <= 0) return 0;
-  if (T == nullptr || T->n_added < 0) return (int)hipErrorInvalidValue;
+  if (T == nullptr || !bpe_params_ok(*T)) return (int)hipErrorInvalidValue;
   const bool sp = T->kind == kBpeSp, cased = bpe_kind_case(T->kind);
   const bool split = bpe_kind_mem_added(T->kind);  // (sp: its added tokens are the split family's)
-  if (sp && (T->ignore_merges || T->nfc || T->sp_ascii == nullptr || T->sp_cp == nullptr || T->byte_id == nullptr ||
-             !bpe_sp_flags_valid(T->sp_flags)))
-    return (int)hipErrorInvalidValue;
-  if (split ? (T->n_added > kBpeSplitMaxAdded || (T->n_added && (T->aoff == nullptr || T->added == nullptr)) ||
-               (T->ignore_merges && (T->vslots == nullptr || T->vpool == nullptr || T->vlongest < 1)))
-            : (T->kind != kBpeGpt2 || T->n_added > kBpeMaxAdded))
-    return (int)hipErrorInvalidValue;
-  if (T->nfc && (!split || T->nfc1 == nullptr || T->nfc2 == nullptr)) return (int)hipErrorInvalidValue;
-  if (cased && (T->ccls1 == nullptr || T->ccls2 == nullptr)) return (int)hipErrorInvalidValue;
   const int grid = n_max < kBpeGrid ? n_max : kBpeGrid;
   // the documents with pre-tokens over kBpeMaxWord bytes (grid-stride; the others are skipped)
   const int grid_long = n_max < kBpeGrid / 4 ? n_max : kBpeGrid / 4;

@@ -100,9 +100,7 @@ __global__ __launch_bounds__(kWpLanes) void k_wp_count_fold(DevWp T, const uint8
 extern "C" int tb_wp_count(hipStream_t stream, const DevWp* T, const uint8_t* text, const int64_t* off,
                            const int64_t* n_dev, int32_t n_max, int32_t* counts) {
   if (n_max <= 0) return 0;
-  if (T == nullptr || T->n_added < 0 || T->n_added > kBpeMaxAdded || T->longest < 1 || T->max_chars < 0)
-    return (int)hipErrorInvalidValue;
-  if (T->fold1 != nullptr && (T->fold2 == nullptr || T->foldp == nullptr)) return (int)hipErrorInvalidValue;
+  if (T == nullptr || !wp_params_ok(*T)) return (int)hipErrorInvalidValue;
   const int grid = n_max < kWpGrid ? n_max : kWpGrid;
   if (T->fold1 != nullptr)
     hipLaunchKernelGGL(k_wp_count_fold, dim3(grid), dim3(kWpLanes), 0, stream, *T, text, off, n_dev, n_max, counts);

@@ -7,26 +7,16 @@
 #include <algorithm>
 #include <cstring>
 #include <optional>
-#include <thread>
 #include <unordered_map>
 
 #include "../common/badwords.h"
-#include "../common/bpe.h"
-#include "../common/bpe_split.h"
-#include "../common/bpe_case.h"
-#include "../common/bpe_sp.h"
-#include "../common/bpe_classes.inc"
-#include "../common/nfc_qc.inc"
-#include "../common/bpe_case_classes.inc"
-#include "../common/wordpiece.h"
-#include "../common/wp_classes.inc"
-#include "../common/wp_fold.inc"
 #include "../common/langid.h"
 #include "../common/ucd_tables.inc"
 #include "filters.h"
 #include "html.h"
 #include "html_entities.inc"
 #include "json.h"
+#include "np_util.h"
 #include "pipeline.h"
 #include "devplan_build.h"
 #include "rustfmt.h"
@@ -35,12 +25,8 @@
 namespace py = pybind11;
 using namespace tb;
 
-template <class T>
-static py::array_t<T> to_numpy(std::vector<T>&& v) {
-  auto* heap = new std::vector<T>(std::move(v));
-  py::capsule owner(heap, [](void* p) { delete reinterpret_cast<std::vector<T>*>(p); });
-  return py::array_t<T>({(py::ssize_t)heap->size()}, {(py::ssize_t)sizeof(T)}, heap->data(), owner);
-}
+void register_tok(py::module_& m);  // tok_module.cpp: the token counters
+
 static py::array_t<uint8_t> str_to_numpy(std::string&& s) {
   auto* heap = new std::string(std::move(s));
   py::capsule owner(heap, [](void* p) { delete reinterpret_cast<std::string*>(p); });
@@ -338,327 +324,7 @@ PYBIND11_MODULE(_tbhost, m) {
   }, py::arg("data"), py::arg("off"), py::arg("table"), py::arg("roots") = py::none(), py::arg("cjk") = py::none(),
      py::arg("root0") = -1, py::arg("cjk0") = 0, py::arg("dead") = py::none(), py::arg("dead_max") = 0,
      py::arg("nthreads") = 8);
-  // ---- byte-level BPE token counting (csrc/common/bpe.h; device kernel csrc/hip/bpe.hip) ----
-  m.def("bpe_classes", []() {
-    std::vector<uint16_t> c1(TB_BPE_CLS_STAGE1, TB_BPE_CLS_STAGE1 + sizeof(TB_BPE_CLS_STAGE1) / 2);
-    std::vector<uint32_t> c2(TB_BPE_CLS_STAGE2, TB_BPE_CLS_STAGE2 + sizeof(TB_BPE_CLS_STAGE2) / 4);
-    return py::make_tuple(to_numpy(std::move(c1)), to_numpy(std::move(c2)));
-  });
-  m.def("bpe_build_table", [](py::array_t<uint32_t, py::array::c_style> a, py::array_t<uint32_t, py::array::c_style> b,
-                              py::array_t<uint32_t, py::array::c_style> rank, py::array_t<uint32_t, py::array::c_style> nid) {
-    // open addressing, load <= 1/2; a pair listed twice keeps its last rank (HashMap collect)
-    const size_t n = (size_t)a.size();
-    if ((size_t)b.size() != n || (size_t)rank.size() != n || (size_t)nid.size() != n)
-      throw std::invalid_argument("bpe_build_table: operand shapes");
-    size_t cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    std::vector<uint64_t> keys(cap, kBpeEmpty), vals(cap, ~0ull);
-    const uint64_t mask = cap - 1;
-    for (size_t i = 0; i < n; ++i) {
-      const uint64_t key = ((uint64_t)a.data()[i] << 32) | b.data()[i];
-      if (key == kBpeEmpty) throw std::invalid_argument("bpe_build_table: reserved pair");
-      uint64_t h = bpe_hash(key) & mask;
-      while (keys[h] != kBpeEmpty && keys[h] != key) h = (h + 1) & mask;
-      keys[h] = key;
-      vals[h] = ((uint64_t)rank.data()[i] << 32) | nid.data()[i];
-    }
-    return py::make_tuple(to_numpy(std::move(keys)), to_numpy(std::move(vals)), (uint32_t)mask);
-  });
-  m.def("bpe_count", [](py::array_t<uint8_t, py::array::c_style> data, py::array_t<int64_t, py::array::c_style> off,
-                        py::array_t<uint32_t, py::array::c_style> byte_id, py::array_t<uint64_t, py::array::c_style> keys,
-                        py::array_t<uint64_t, py::array::c_style> vals, uint32_t mask,
-                        py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
-                        int nthreads, int64_t chunk, int kind, bool ignore_merges,
-                        py::array_t<uint64_t, py::array::c_style> vslots, uint32_t vmask,
-                        py::array_t<uint8_t, py::array::c_style> vpool, int32_t vlongest, bool nfc,
-                        py::array_t<uint32_t, py::array::c_style> sp_ascii,
-                        py::array_t<uint64_t, py::array::c_style> sp_cp, uint32_t sp_mask, uint32_t sp_id,
-                        int32_t sp_flags) {
-    // host emulation of k_bpe_count / k_bpe_split_count / k_bpe_sp_count (kind: BpeKind): per document the token
-    // count, or kBpeHost. chunk > 0: the wave split — the pre-tokens starting in each chunk-byte
-    // range counted independently (bpe_count_range), as the kernel's lanes do. nfc: behind the NFC
-    // gate (bpe_nfc_range, per range in the chunk mode), as k_bpe_split_count_nfc
-    const bool sp = kind == kBpeSp, split = bpe_kind_split(kind) || sp;  // (split: added tokens in memory)
-    if (byte_id.size() != 256 || (size_t)keys.size() != (size_t)mask + 1 || vals.size() != keys.size() ||
-        (!split && kind != kBpeGpt2) || added_off.size() > (size_t)(split ? kBpeSplitMaxAdded : kBpeMaxAdded) + 1 ||
-        (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size())) ||
-        !std::is_sorted(added_off.begin(), added_off.end()) || (ignore_merges && !split) || (nfc && !split) ||
-        (ignore_merges && ((size_t)vslots.size() != 2 * ((size_t)vmask + 1) || vlongest < 1)) ||
-        (sp && (ignore_merges || nfc || sp_ascii.size() != 128 || (size_t)sp_cp.size() != (size_t)sp_mask + 1 ||
-                !bpe_sp_flags_valid(sp_flags))))
-      throw std::invalid_argument("bpe_count: operand shapes");
-    if (sp) {  // a free slot ends every probe
-      bool free_slot = false;
-      for (size_t i = 0; i <= sp_mask; ++i) free_slot = free_slot || sp_cp.data()[i] == kBpeSpEmpty;
-      if (!free_slot) throw std::invalid_argument("bpe_count: code point table");
-    }
-    if (ignore_merges)  // every listed entry lies in the pool
-      for (size_t i = 0; i <= vmask; ++i) {
-        const uint64_t v = vslots.data()[2 * i + 1];
-        if (v != kWpEmpty && (v >> 32) + (uint32_t)v > (uint64_t)vpool.size())
-          throw std::invalid_argument("bpe_count: vocabulary table");
-      }
-    const int64_t nd = off.size() - 1;
-    std::vector<int32_t> out(nd > 0 ? nd : 0);
-    DevBpe T{};
-    T.byte_id = byte_id.data();
-    T.keys = keys.data();
-    T.vals = vals.data();
-    T.cls1 = TB_BPE_CLS_STAGE1;
-    T.cls2 = TB_BPE_CLS_STAGE2;
-    T.added = added.data();
-    T.mask = mask;
-    T.n_added = added_off.empty() ? 0 : (int32_t)added_off.size() - 1;
-    if (split) {
-      T.aoff = added_off.data();
-      bpe_added_mask(T.added, T.aoff, T.n_added, T.amask);
-      T.vslots = vslots.data();
-      T.vpool = vpool.data();
-      T.vmask = vmask;
-      T.vlongest = vlongest;
-      T.ignore_merges = ignore_merges;
-    } else {
-      for (size_t i = 0; i < added_off.size(); ++i) T.added_off[i] = added_off[i];
-    }
-    T.kind = kind;
-    T.post_add = post_add;
-    T.ccls1 = TB_BPE_CASE_STAGE1;
-    T.ccls2 = TB_BPE_CASE_STAGE2;
-    T.nfc1 = TB_NFC_QC_STAGE1;
-    T.nfc2 = TB_NFC_QC_STAGE2;
-    T.nfc = nfc;
-    T.sp_ascii = sp_ascii.data();
-    T.sp_cp = sp_cp.data();
-    T.sp_mask = sp_mask;
-    T.sp_id = sp_id;
-    T.sp_flags = sp_flags;
-    const uint8_t* d = data.data();
-    const int64_t* o = off.data();
-    auto run = [&](auto policy) {
-      using P = decltype(policy);
-      py::gil_scoped_release nogil;
-      const int nt = std::max(1, std::min<int>(nthreads, (int)(nd / 256) + 1));
-      std::vector<std::thread> th;
-      for (int t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() {
-          uint32_t cbuf[kBpeMaxWord], rbuf[kBpeMaxWord];
-          std::vector<uint32_t> lc(kBpeMaxLong);
-          std::vector<uint64_t> lv(kBpeMaxLong);
-          std::vector<int32_t> lnx(kBpeMaxLong), lpv(kBpeMaxLong);
-          const uint8_t* b = nullptr;
-          int64_t n = 0;
-          // pre-tokens over kBpeMaxWord bytes: merged over arrays of their own length (as
-          // k_bpe_long does), up to kBpeMaxLong bytes
-          auto on_long = [&](int64_t s, int64_t e) -> int64_t {
-            const int lead = P::lead(T, b, n, s);
-            if (e - s + lead > kBpeMaxLong) return -1;
-            return bpe_word_long<P>(T, b + s, (int)(e - s), lc.data(), lv.data(), lnx.data(), lpv.data(), lead);
-          };
-          for (int64_t k = t; k < nd; k += nt) {
-            b = d + o[k];
-            n = o[k + 1] - o[k];
-            if (chunk <= 0) {
-              out[k] = bpe_count_doc<P>(T, b, n, BpeArr{cbuf, 1}, BpeArr{rbuf, 1}, on_long);
-              continue;
-            }
-            int64_t tot = T.post_add;
-            bool bad = T.n_added && P::has_added(T, b, n, 0, n);
-            for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
-              if (T.nfc && bpe_nfc_range(T, b, n, s0, std::min(n, s0 + chunk)) != 1) {
-                bad = true;
-                break;
-              }
-              const int64_t x = bpe_count_range<true, P>(T, b, n, s0, std::min(n, s0 + chunk), BpeArr{cbuf, 1},
-                                                         BpeArr{rbuf, 1}, on_long);
-              if (x < 0) bad = true;
-              tot += x;
-            }
-            out[k] = (bad || tot > 0x7FFFFFFF) ? kBpeHost : (int32_t)tot;
-          }
-        });
-      for (auto& x : th) x.join();
-    };
-    if (bpe_kind_case(kind)) run(BpeCase{});
-    else if (sp) run(BpeSp{});
-    else if (split) run(BpeSplit{});
-    else run(BpeGpt2{});
-    return to_numpy(std::move(out));
-  }, py::arg("data"), py::arg("off"), py::arg("byte_id"), py::arg("keys"), py::arg("vals"), py::arg("mask"),
-        py::arg("added"), py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0,
-        py::arg("kind") = 0, py::arg("ignore_merges") = false,
-        py::arg("vslots") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("vmask") = 0,
-        py::arg("vpool") = py::array_t<uint8_t, py::array::c_style>(0), py::arg("vlongest") = 0,
-        py::arg("nfc") = false, py::arg("sp_ascii") = py::array_t<uint32_t, py::array::c_style>(0),
-        py::arg("sp_cp") = py::array_t<uint64_t, py::array::c_style>(0), py::arg("sp_mask") = 0, py::arg("sp_id") = 0,
-        py::arg("sp_flags") = 0);
-  m.def("bpe_sp_build_table", [](py::array_t<uint32_t, py::array::c_style> cps, py::array_t<uint32_t, py::array::c_style> ids) {
-    // DevBpe::sp_cp (csrc/common/bpe_sp.h): code point -> id of the single-character vocabulary
-    // entries above ASCII
-    const size_t n = (size_t)cps.size();
-    if ((size_t)ids.size() != n) throw std::invalid_argument("bpe_sp_build_table: operand shapes");
-    for (size_t i = 0; i < n; ++i)
-      if (cps.data()[i] < 128 || cps.data()[i] > 0x10FFFF) throw std::invalid_argument("bpe_sp_build_table: code point");
-    size_t cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    std::vector<uint64_t> slots(cap);
-    bpe_sp_fill(cps.data(), ids.data(), n, slots.data(), (uint32_t)(cap - 1));
-    return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)(cap - 1));
-  });
-  m.def("nfc_qc", []() {
-    // the NFC gate's two-stage table (csrc/common/nfc_qc.inc)
-    std::vector<uint8_t> t1(TB_NFC_QC_STAGE1, TB_NFC_QC_STAGE1 + sizeof(TB_NFC_QC_STAGE1));
-    std::vector<uint8_t> t2(TB_NFC_QC_STAGE2, TB_NFC_QC_STAGE2 + sizeof(TB_NFC_QC_STAGE2));
-    return py::make_tuple(to_numpy(std::move(t1)), to_numpy(std::move(t2)));
-  });
-  m.def("bpe_case_classes", []() {
-    std::vector<uint16_t> c1(TB_BPE_CASE_STAGE1, TB_BPE_CASE_STAGE1 + sizeof(TB_BPE_CASE_STAGE1) / 2);
-    std::vector<uint32_t> c2(TB_BPE_CASE_STAGE2, TB_BPE_CASE_STAGE2 + sizeof(TB_BPE_CASE_STAGE2) / 4);
-    return py::make_tuple(to_numpy(std::move(c1)), to_numpy(std::move(c2)));
-  });
-  m.def("bpe_split_ends", [](py::bytes text, int kind) -> py::object {
-    // the pre-tokens of pattern A / B (bpe_split_next_token) or C / D (bpe_case_next_token): their
-    // end offsets in bytes, None on invalid UTF-8 (for tests and tools that compare the rules with
-    // the library's Split)
-    if (!bpe_kind_split(kind)) throw std::invalid_argument("bpe_split_ends: kind");
-    const std::string s = text;
-    DevBpe T{};
-    T.cls1 = TB_BPE_CLS_STAGE1;
-    T.cls2 = TB_BPE_CLS_STAGE2;
-    T.ccls1 = TB_BPE_CASE_STAGE1;
-    T.ccls2 = TB_BPE_CASE_STAGE2;
-    T.kind = kind;
-    std::vector<int64_t> ends;
-    const int64_t n = (int64_t)s.size();
-    for (int64_t p = 0; p < n;) {
-      const uint8_t* u = reinterpret_cast<const uint8_t*>(s.data());
-      const int64_t e = bpe_kind_case(kind) ? bpe_case_next_token(T, u, n, p) : bpe_split_next_token(T, u, n, p);
-      if (e <= p) return py::none();
-      ends.push_back(e);
-      p = e;
-    }
-    return to_numpy(std::move(ends));
-  });
-  m.def("bpe_added_mask", [](py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off) {
-    // DevBpe::amask: the 256-bit mask of the added tokens' first bytes
-    if (added_off.size() && (added_off[0] != 0 || added_off.back() > added.size() ||
-                             !std::is_sorted(added_off.begin(), added_off.end())))
-      throw std::invalid_argument("bpe_added_mask: operand shapes");
-    std::vector<uint64_t> m4(4);
-    bpe_added_mask(added.data(), added_off.data(), added_off.empty() ? 0 : (int)added_off.size() - 1, m4.data());
-    return to_numpy(std::move(m4));
-  });
-  // ---- WordPiece token counting (csrc/common/wordpiece.h; device kernel csrc/hip/wordpiece.hip) ----
-  m.def("wp_classes", []() {
-    std::vector<uint16_t> c1(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE1 + sizeof(TB_WP_CLS_STAGE1) / 2);
-    std::vector<uint8_t> c2(TB_WP_CLS_STAGE2, TB_WP_CLS_STAGE2 + sizeof(TB_WP_CLS_STAGE2));
-    return py::make_tuple(to_numpy(std::move(c1)), to_numpy(std::move(c2)));
-  });
-  m.def("wp_ascii", [](uint32_t shift) {
-    std::vector<uint64_t> a(4);
-    wp_ascii_classes(TB_WP_CLS_STAGE1, TB_WP_CLS_STAGE2, shift, a.data());
-    return to_numpy(std::move(a));
-  });
-  m.def("wp_fold_tables", []() {
-    // wp_fold.inc for upload: stage 1 of the three modes (lowercase, strip_accents, both), the
-    // shared stage 2 and the record pool
-    std::vector<uint16_t> f1(TB_WP_FOLD_STAGE1, TB_WP_FOLD_STAGE1 + sizeof(TB_WP_FOLD_STAGE1) / 2);
-    std::vector<uint16_t> f2(TB_WP_FOLD_STAGE2, TB_WP_FOLD_STAGE2 + sizeof(TB_WP_FOLD_STAGE2) / 2);
-    std::vector<uint8_t> fp(TB_WP_FOLD_POOL, TB_WP_FOLD_POOL + sizeof(TB_WP_FOLD_POOL));
-    return py::make_tuple(to_numpy(std::move(f1)).attr("reshape")(3, TB_WP_FOLD_NSTAGE1), to_numpy(std::move(f2)),
-                          to_numpy(std::move(fp)));
-  });
-  m.def("wp_build_table", [](py::array_t<uint8_t, py::array::c_style> pool, py::array_t<int64_t, py::array::c_style> off,
-                             py::array_t<uint8_t, py::array::c_style> cont) {
-    // pieces i = (cont[i], pool[off[i]:off[i + 1]]), distinct; open addressing, load <= 1/2.
-    // Returns the slots as uint64 pairs (WpSlot), the mask and the longest piece's bytes.
-    const size_t n = (size_t)cont.size();
-    if ((size_t)off.size() != n + 1 || n >= (1u << 30)) throw std::invalid_argument("wp_build_table: operand shapes");
-    const int64_t* o = off.data();
-    for (size_t i = 0; i < n; ++i)
-      if (o[i] < 0 || o[i + 1] <= o[i] || o[i + 1] > pool.size() || o[i + 1] - o[i] >= (1ll << 31) ||
-          o[i] >= (1ll << 32) || cont.data()[i] > 1)
-        throw std::invalid_argument("wp_build_table: piece offsets");
-    size_t cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    static_assert(sizeof(WpSlot) == 16, "WpSlot is two uint64");
-    std::vector<uint64_t> slots(2 * cap, kWpEmpty);
-    const uint64_t mask = cap - 1;
-    const int64_t longest =
-        wp_fill_slots(pool.data(), o, cont.data(), n, reinterpret_cast<WpSlot*>(slots.data()), mask);
-    return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)mask, longest);
-  });
-  m.def("wp_count", [](py::array_t<uint8_t, py::array::c_style> data, py::array_t<int64_t, py::array::c_style> off,
-                       py::array_t<uint64_t, py::array::c_style> slots, uint32_t mask,
-                       py::array_t<uint8_t, py::array::c_style> pool, uint32_t flags, uint32_t cls_shift,
-                       uint32_t self_bit, int32_t max_chars, int32_t longest,
-                       py::array_t<uint8_t, py::array::c_style> added, std::vector<int32_t> added_off, int32_t post_add,
-                       int nthreads, int64_t chunk, int fold) {
-    // host emulation of k_wp_count (fold 0) / k_wp_count_fold (fold 1 lowercase, 2 strip_accents,
-    // 3 both: wp_fold.inc): per document the token count, or kBpeHost. chunk > 0: the wave split -
-    // the words starting in each chunk-byte range counted independently (wp_count_range), as the
-    // kernel's lanes do
-    if ((size_t)slots.size() != 2 * ((size_t)mask + 1) || added_off.size() > kBpeMaxAdded + 1 ||
-        (added_off.size() && added_off.back() > added.size()) || (cls_shift != 0 && cls_shift != 2) || longest < 1 ||
-        max_chars < 0 || fold < 0 || fold > 3)
-      throw std::invalid_argument("wp_count: operand shapes");
-    static_assert(sizeof(WpSlot) == 16, "WpSlot is two uint64");
-    const int64_t nd = off.size() - 1;
-    std::vector<int32_t> out(nd > 0 ? nd : 0);
-    DevWp T{};
-    T.slots = reinterpret_cast<const WpSlot*>(slots.data());
-    T.pool = pool.data();
-    T.cls1 = TB_WP_CLS_STAGE1;
-    T.cls2 = TB_WP_CLS_STAGE2;
-    T.added = added.data();
-    if (fold) {
-      T.fold1 = TB_WP_FOLD_STAGE1 + (size_t)(fold - 1) * TB_WP_FOLD_NSTAGE1;
-      T.fold2 = TB_WP_FOLD_STAGE2;
-      T.foldp = TB_WP_FOLD_POOL;
-    }
-    uint64_t asc[4];
-    wp_ascii_classes(T.cls1, T.cls2, cls_shift, asc);
-    T.asc0 = asc[0]; T.asc1 = asc[1]; T.asc2 = asc[2]; T.asc3 = asc[3];
-    T.mask = mask;
-    T.flags = flags;
-    T.cls_shift = cls_shift;
-    T.self_bit = self_bit;
-    T.max_chars = max_chars;
-    T.longest = longest;
-    T.post_add = post_add;
-    T.n_added = added_off.empty() ? 0 : (int32_t)added_off.size() - 1;
-    for (size_t i = 0; i < added_off.size(); ++i) T.added_off[i] = added_off[i];
-    const uint8_t* d = data.data();
-    const int64_t* o = off.data();
-    {
-      py::gil_scoped_release nogil;
-      const int nt = std::max(1, std::min<int>(nthreads, (int)(nd / 256) + 1));
-      std::vector<std::thread> th;
-      for (int t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() {
-          for (int64_t k = t; k < nd; k += nt) {
-            const uint8_t* b = d + o[k];
-            const int64_t n = o[k + 1] - o[k];
-            if (chunk <= 0) {
-              out[k] = fold ? wp_count_doc_t<true>(T, b, n) : wp_count_doc(T, b, n);
-              continue;
-            }
-            int64_t tot = T.post_add;
-            bool bad = T.n_added && wp_has_added(T, b, n, 0, n);
-            for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
-              const int64_t s1 = std::min(n, s0 + chunk);
-              const int64_t x = fold ? wpf_count_range(T, b, n, s0, s1) : wp_count_range(T, b, n, s0, s1);
-              if (x < 0) bad = true;
-              tot += x;
-            }
-            out[k] = (bad || tot > 0x7FFFFFFF) ? kBpeHost : (int32_t)tot;
-          }
-        });
-      for (auto& x : th) x.join();
-    }
-    return to_numpy(std::move(out));
-  }, py::arg("data"), py::arg("off"), py::arg("slots"), py::arg("mask"), py::arg("pool"), py::arg("flags"),
-        py::arg("cls_shift"), py::arg("self_bit"), py::arg("max_chars"), py::arg("longest"), py::arg("added"),
-        py::arg("added_off"), py::arg("post_add"), py::arg("nthreads") = 8, py::arg("chunk") = 0, py::arg("fold") = 0);
+  register_tok(m);
   m.def("fmt_f64", [](double x) { return fmt_f64(x); });
   m.def("fmt_fixed", [](double x, int prec) { return fmt_fixed(x, prec); });
   m.def("contains_byte", [](py::array_t<uint8_t, py::array::c_style> a, int v) {

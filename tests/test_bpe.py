@@ -52,8 +52,7 @@ def native_counts(model, texts):
     data, off = synth.pack(texts)
     sp = model.bpe_spec()
     assert sp is not None
-    raw = native.host().bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off,
-                                  sp.post_add, 4)
+    raw = native.host().bpe_count(data, off, sp, 4)
     return raw, model.count_native(data, off, 4)
 
 
@@ -188,37 +187,20 @@ def test_emulated_device_token_counts_equal_cpu(trained):
 
 @pytest.mark.gpu
 def test_device_token_counts_equal_cpu(trained):
-    from test_emulated_device_path import outputs
+    import tok_device
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.pipeline.engine import Engine
-
-    assert hiprt.device_count() > 0
     texts = synth.make_corpus(6000, 1000, seed=14) + fuzz(400, 15) + ["<|endoftext|> is here and so are we all."]
     data, off = synth.pack(texts)
-    eng = Engine(_cfg(), backend="cuda", keep_reasons=True, tokenizer_file=trained)
-    assert eng.device_runner.resolve_t is not None and eng.device_runner.bpe
-    a = eng.process(data, off)
-    b = Engine(_cfg(), backend="cpu", nthreads=8, keep_reasons=True, tokenizer_file=trained,
-               segmentation="icu").process(data, off)
-    np.testing.assert_array_equal(a.status, b.status)
-    assert outputs(a) == outputs(b)
+    tok_device.device_and_cpu(_cfg, trained, data, off)
 
 
 @pytest.mark.gpu
 def test_bpe_kernel_equals_host(trained):
     """k_bpe_count directly on packed documents (no K16 count pointer) vs the host emulation."""
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
+    import tok_device
 
     m = TokenCounterModel(trained)
     texts = corpus()
     data, off = synth.pack(texts)
     raw, _ = native_counts(m, texts)
-    k = Kernels(0)
-    tabs = k.bpe_tables(m.bpe_spec())
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    out = hiprt.zeros(len(texts), np.int32)
-    k.bpe_count(tabs, d_text, d_off, None, len(texts), out)
-    np.testing.assert_array_equal(out.to_host(), raw)
+    tok_device.assert_kernels_equal(m.bpe_spec(), data, off, raw, tables="bpe_tables", count="bpe_count")

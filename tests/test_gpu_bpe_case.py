@@ -7,12 +7,12 @@ import importlib.util
 import os
 import sys
 
-import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bpe_case_corpus as cc  # noqa: E402
 import bpe_split_corpus as bc  # noqa: E402
+import tok_device  # noqa: E402
 
 from textblaster_amd.models.tokenizer import TokenCounterModel, count_spec, train_synthetic_split_bpe  # noqa: E402
 from textblaster_amd.utils import synth  # noqa: E402
@@ -76,9 +76,6 @@ def test_case_and_nfc_kernels_equal_host(tok_dir, pattern, ignore_merges, nfc):
     """The kernels directly on packed documents (no K16 count pointer) vs the host emulation."""
     from tokenizers import normalizers
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
-
     m = TokenCounterModel(_tokenizer(tok_dir, pattern, ignore_merges, nfc))
     docs, host = cc.corpus()
     edges = lane_edge_docs()
@@ -102,13 +99,7 @@ def test_case_and_nfc_kernels_equal_host(tok_dir, pattern, ignore_merges, nfc):
         assert not any(r >= 0 and nz(t) != t for r, t in zip(raw.tolist(), texts))
     else:
         assert (raw >= 0).sum() >= len(texts) - len(host) - 5
-    k = Kernels(0)
-    tabs = k.token_tables(sp)
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    out = hiprt.zeros(len(texts), np.int32)
-    k.token_count(tabs, d_text, d_off, None, len(texts), out)
-    np.testing.assert_array_equal(out.to_host(), raw)
+    tok_device.assert_kernels_equal(sp, data, off, raw)
 
 
 @pytest.mark.parametrize("pattern,ignore_merges,nfc", [("B", False, True), ("C", True, False)], ids=["B-nfc", "C"])
@@ -117,29 +108,13 @@ def test_device_token_counts_equal_cpu(tok_dir, pattern, ignore_merges, nfc):
     that NFC changes or that hold a code point the gate does not resolve (none without the
     normalizer, none in the synthetic part), and statuses and outputs equal the CPU path's."""
     from test_bpe import _cfg
-    from test_emulated_device_path import outputs
     from tokenizers import normalizers
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.pipeline.engine import Engine
-    from textblaster_amd.utils import metrics
-
-    assert hiprt.device_count() > 0
     tok = _tokenizer(tok_dir, pattern, ignore_merges, nfc)
     synth_docs = synth.make_corpus(6000, 1000, seed=14)
     texts = synth_docs + cc.fuzz(400, 15)
     data, off = synth.pack(texts)
-    eng = Engine(_cfg(), backend="cuda", keep_reasons=True, tokenizer_file=tok)
-    assert eng.device_runner.resolve_t is not None and eng.device_runner.bpe
-    h0, d0 = metrics.BPE_HOST_DOCS_TOTAL._value.get(), metrics.BPE_DEVICE_DOCS_TOTAL._value.get()
-    a = eng.process(data, off)
-    nh = metrics.BPE_HOST_DOCS_TOTAL._value.get() - h0
-    nd = metrics.BPE_DEVICE_DOCS_TOTAL._value.get() - d0
-    b = Engine(_cfg(), backend="cpu", nthreads=8, keep_reasons=True, tokenizer_file=tok,
-               segmentation="icu").process(data, off)
-    np.testing.assert_array_equal(a.status, b.status)
-    oa = outputs(a)
-    assert oa == outputs(b)
+    a, oa, nh, nd = tok_device.device_and_cpu(_cfg, tok, data, off)
     want = 0
     if nfc:
         spec = importlib.util.spec_from_file_location("gen_nfc_qc", os.path.join(REPO, "tools", "gen_nfc_qc.py"))

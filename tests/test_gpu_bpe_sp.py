@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bpe_sp_corpus as sc  # noqa: E402
+import tok_device  # noqa: E402
 
 from textblaster_amd.models.tokenizer import BPE_SP, TokenCounterModel, count_spec  # noqa: E402
 from textblaster_amd.utils import synth  # noqa: E402
@@ -49,9 +50,6 @@ def lane_edge_docs():
 @pytest.mark.parametrize("name", ["L-prepend", "L-plain", "M-first-split"])
 def test_sp_kernels_equal_host(tok_dir, name):
     """The kernels directly on packed documents (no K16 count pointer) vs the host emulation."""
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
-
     _, prepend, split = sc.VARIANTS[name]
     m = TokenCounterModel(sc.tokenizer(tok_dir, name))
     texts = sc.corpus() + lane_edge_docs() + sc.INVALID
@@ -66,13 +64,7 @@ def test_sp_kernels_equal_host(tok_dir, name):
     assert by_text[SPACES] == (3073 if split else -2)
     assert by_text[CJK_EMOJI] > 2048 // 7 * 4 and by_text[_cut(sc.UNIT * 6000, 200 * 1024)] > 10000
     assert (by_text["q" * 64] > 0) and (by_text["q" * 2048] == -2) == (prepend != 0)
-    k = Kernels(0)
-    tabs = k.token_tables(sp)
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    out = hiprt.zeros(len(texts), np.int32)
-    k.token_count(tabs, d_text, d_off, None, len(texts), out)
-    np.testing.assert_array_equal(out.to_host(), raw)
+    tok_device.assert_kernels_equal(sp, data, off, raw)
 
 
 @pytest.mark.parametrize("name", ["L-prepend", "M-first-split"])
@@ -81,29 +73,13 @@ def test_device_token_counts_equal_cpu(tok_dir, name):
     the rule names (an added token's text, a chunk over 2048 bytes), the device counts the rest, and
     statuses and outputs equal the CPU path's."""
     from test_bpe import _cfg
-    from test_emulated_device_path import outputs
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.pipeline.engine import Engine
-    from textblaster_amd.utils import metrics
-
-    assert hiprt.device_count() > 0
     _, prepend, split = sc.VARIANTS[name]
     tok = sc.tokenizer(tok_dir, name)
     texts = synth.make_corpus(6000, 1000, seed=14) + sc.fuzz(400, 15)
     texts += [t.replace(" ", " </s> ", 1) for t in texts[:60]]  # kept documents for the host tokenizer
     data, off = synth.pack(texts)
-    eng = Engine(_cfg(), backend="cuda", keep_reasons=True, tokenizer_file=tok)
-    assert eng.device_runner.resolve_t is not None and eng.device_runner.bpe
-    h0, d0 = metrics.BPE_HOST_DOCS_TOTAL._value.get(), metrics.BPE_DEVICE_DOCS_TOTAL._value.get()
-    a = eng.process(data, off)
-    nh = metrics.BPE_HOST_DOCS_TOTAL._value.get() - h0
-    nd = metrics.BPE_DEVICE_DOCS_TOTAL._value.get() - d0
-    b = Engine(_cfg(), backend="cpu", nthreads=8, keep_reasons=True, tokenizer_file=tok,
-               segmentation="icu").process(data, off)
-    np.testing.assert_array_equal(a.status, b.status)
-    oa = outputs(a)
-    assert oa == outputs(b)
+    a, oa, nh, nd = tok_device.device_and_cpu(_cfg, tok, data, off)
     kept = [t.decode("utf-8") for kind, t, _ in oa.values() if kind == "kept"]
     assert len(kept) == a.n_kept
     want = sum(sc.to_host(t, prepend, split) for t in kept)

@@ -5,11 +5,11 @@ the CPU path."""
 import os
 import sys
 
-import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bpe_split_corpus as bc  # noqa: E402
+import tok_device  # noqa: E402
 
 from textblaster_amd.models.tokenizer import TokenCounterModel, count_spec, train_synthetic_split_bpe  # noqa: E402
 from textblaster_amd.utils import synth  # noqa: E402
@@ -43,9 +43,6 @@ def lane_edge_docs():
 @pytest.mark.parametrize("pattern,ignore_merges", [("A", True), ("B", False)], ids=["A-ignore_merges", "B-merges"])
 def test_split_kernel_equals_host(tok_dir, pattern, ignore_merges):
     """The kernels directly on packed documents (no K16 count pointer) vs the host emulation."""
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
-
     m = TokenCounterModel(_tokenizer(tok_dir, pattern, ignore_merges))
     docs, host = bc.corpus()
     texts = docs + lane_edge_docs()
@@ -57,35 +54,14 @@ def test_split_kernel_equals_host(tok_dir, pattern, ignore_merges):
     assert all(raw[k] == -2 for k in host) and (raw >= 0).sum() >= len(texts) - len(host) - 2
     assert by_text["q" * 2049 + " tail"] == -2 and by_text["q" * 2048 + " tail"] > 0
     assert by_text["0123456789" + bc.ADDED + " and more text after it"] == -2
-    k = Kernels(0)
-    tabs = k.token_tables(sp)
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    out = hiprt.zeros(len(texts), np.int32)
-    k.token_count(tabs, d_text, d_off, None, len(texts), out)
-    np.testing.assert_array_equal(out.to_host(), raw)
+    tok_device.assert_kernels_equal(sp, data, off, raw)
 
 
 def test_device_token_counts_equal_cpu(tok_dir):
     from test_bpe import _cfg
-    from test_emulated_device_path import outputs
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.pipeline.engine import Engine
-    from textblaster_amd.utils import metrics
-
-    assert hiprt.device_count() > 0
     tok = _tokenizer(tok_dir, "A", True)
     texts = synth.make_corpus(6000, 1000, seed=14) + bc.fuzz(400, 15)
     data, off = synth.pack(texts)
-    eng = Engine(_cfg(), backend="cuda", keep_reasons=True, tokenizer_file=tok)
-    assert eng.device_runner.resolve_t is not None and eng.device_runner.bpe
-    h0, d0 = metrics.BPE_HOST_DOCS_TOTAL._value.get(), metrics.BPE_DEVICE_DOCS_TOTAL._value.get()
-    a = eng.process(data, off)
-    nh = metrics.BPE_HOST_DOCS_TOTAL._value.get() - h0
-    nd = metrics.BPE_DEVICE_DOCS_TOTAL._value.get() - d0
+    a, _, nh, nd = tok_device.device_and_cpu(_cfg, tok, data, off)
     assert nh == 0 and nd == a.n_kept > 0  # every kept document counted by the kernels
-    b = Engine(_cfg(), backend="cpu", nthreads=8, keep_reasons=True, tokenizer_file=tok,
-               segmentation="icu").process(data, off)
-    np.testing.assert_array_equal(a.status, b.status)
-    assert outputs(a) == outputs(b)

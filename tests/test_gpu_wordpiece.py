@@ -4,10 +4,10 @@ trailing WordPiece TokenCounter against the CPU path."""
 import os
 import sys
 
-import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tok_device  # noqa: E402
 import wordpiece_corpus as wc  # noqa: E402
 
 from textblaster_amd.models.tokenizer import TokenCounterModel, count_spec, train_synthetic_wordpiece  # noqa: E402
@@ -41,39 +41,19 @@ def lane_edge_docs():
 @pytest.mark.parametrize("lowercase", [False, True], ids=["cased", "uncased"])
 def test_wp_kernel_equals_host(tok_dir, lowercase):
     """k_wp_count directly on packed documents (no K16 count pointer) vs the host emulation."""
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
-
     m = TokenCounterModel(_tokenizer(tok_dir, lowercase))
     texts = wc.corpus("the") + lane_edge_docs()
     data, off = synth.pack(texts)
     sp = m.wordpiece_spec()
     raw = count_spec(sp, data, off, 8)
     assert (raw >= 0).sum() > 1000
-    k = Kernels(0)
-    tabs = k.wp_tables(sp)
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    out = hiprt.zeros(len(texts), np.int32)
-    k.wp_count(tabs, d_text, d_off, None, len(texts), out)
-    np.testing.assert_array_equal(out.to_host(), raw)
+    tok_device.assert_kernels_equal(sp, data, off, raw, tables="wp_tables", count="wp_count")
 
 
 def test_device_token_counts_equal_cpu(tok_dir):
-    from test_emulated_device_path import outputs
     from test_wordpiece import _cfg
 
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.pipeline.engine import Engine
-
-    assert hiprt.device_count() > 0
     tok = _tokenizer(tok_dir, False)
     texts = synth.make_corpus(6000, 1000, seed=14) + wc.fuzz(400, 15)
     data, off = synth.pack(texts)
-    eng = Engine(_cfg(), backend="cuda", keep_reasons=True, tokenizer_file=tok)
-    assert eng.device_runner.resolve_t is not None and eng.device_runner.bpe
-    a = eng.process(data, off)
-    b = Engine(_cfg(), backend="cpu", nthreads=8, keep_reasons=True, tokenizer_file=tok,
-               segmentation="icu").process(data, off)
-    np.testing.assert_array_equal(a.status, b.status)
-    assert outputs(a) == outputs(b)
+    tok_device.device_and_cpu(_cfg, tok, data, off)

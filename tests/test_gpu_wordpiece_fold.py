@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tok_device  # noqa: E402
 import wordpiece_corpus as wc  # noqa: E402
 import wordpiece_fold_corpus as fc  # noqa: E402
 
@@ -40,8 +41,7 @@ def lane_edge_docs():
 
 @pytest.mark.parametrize("mode", list(MODES))
 def test_fold_kernel_equals_host(tok_dir, mode):
-    from textblaster_amd.ops import hiprt
-    from textblaster_amd.ops.kernels import Kernels
+    from textblaster_amd import native
 
     lower, strip = MODES[mode]
     m = TokenCounterModel(fc.train(str(tok_dir / f"{mode}.json"), lower, strip))
@@ -55,15 +55,9 @@ def test_fold_kernel_equals_host(tok_dir, mode):
     ident = count_spec(m.wordpiece_spec(), data, off, 8)
     assert (raw >= 0).sum() >= 1000
     assert ((raw >= 0) & (ident == -2)).sum() >= 500
-    k = Kernels(0)
-    tabs = k.wp_tables(sp)
-    assert tabs.struct.fold1 and tabs.struct.fold2 and tabs.struct.foldp
-    d_text = hiprt.to_device(np.concatenate([data, np.zeros(16, np.uint8)]))
-    d_off = hiprt.to_device(off)
-    for _ in range(2):
-        out = hiprt.zeros(len(texts), np.int32)
-        k.wp_count(tabs, d_text, d_off, None, len(texts), out)
-        np.testing.assert_array_equal(out.to_host(), raw)
+    tabs = tok_device.assert_kernels_equal(sp, data, off, raw, runs=2, tables="wp_tables", count="wp_count")
+    offsets = native.host().DEV_WP_OFFSETS
+    assert all(tok_device.block_pointer(tabs.block, offsets, f) for f in ("fold1", "fold2", "foldp"))
 
 
 def test_device_engine_counts_uncased_text(tok_dir):

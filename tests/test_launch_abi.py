@@ -50,6 +50,9 @@ def test_launch_struct_sizes_match_the_library(lib):
     assert K.ABI_VERSION == lib.tb_abi_version()
     for st, sizeof in K.LAUNCH_STRUCTS.items():
         assert ctypes.sizeof(st) == getattr(lib, sizeof)(), st.__name__
+    # the token counters' blocks have no mirror: the host module builds them as bytes
+    assert lib.tb_sizeof_bpe() == native.host().SIZEOF_DEV_BPE
+    assert lib.tb_sizeof_wp() == native.host().SIZEOF_DEV_WP
 
 
 def test_struct_arguments_are_typed(lib):

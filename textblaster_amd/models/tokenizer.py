@@ -27,6 +27,10 @@ The SentencePiece-converted character-level BPE files with ``byte_fallback`` (Ll
 normalizer Prepend + Replace(" ", "▁") and no pre-tokenizer, or a Metaspace pre-tokenizer) get a
 :class:`BpeSpec` of kind ``BPE_SP`` (csrc/common/bpe_sp.h, k_bpe_sp_count): the ids of the
 single-character entries, of the 256 ``<0xNN>`` tokens and of ``▁``, and the prepend and split rules.
+
+A spec is data only. The host module reads it as it stands (``bpe_count`` / ``wp_count`` for the host
+emulation, ``bpe_params`` / ``wp_params`` for the kernels' parameter block), and one validator and
+one filler there (csrc/host/tok_params.h) decide whether it is usable and write the block for both.
 """
 from __future__ import annotations
 
@@ -74,7 +78,31 @@ def bytes_to_unicode() -> List[str]:
     return [chr(m[b]) for b in range(256)]
 
 
-MAX_ADDED = 8  # csrc/common/bpe.h kBpeMaxAdded
+MAX_ADDED = 8  # csrc/common/bpe.h kBpeMaxAdded (this and the constants below: pinned to the headers' values by
+# tests/test_tok_params.py through the host module's TOK_CONSTANTS)
+
+
+def _u32(v) -> np.ndarray:
+    return np.array(v, dtype=np.uint32)
+
+
+def _pack_added(contents: List[str]):
+    """The added tokens' contents as the specs carry them: their UTF-8 bytes concatenated (one zero
+    byte when there are none) and the n + 1 offsets ([] when there are none)."""
+    added = [c.encode("utf-8") for c in contents]
+    off = [0]
+    for t in added:
+        off.append(off[-1] + len(t))
+    return np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(), off if added else []
+
+
+def _save_atomically(path: str, write) -> str:
+    """``write(tmp)`` then rename onto ``path``: a concurrent reader never sees a partial file."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    write(tmp)
+    os.replace(tmp, path)
+    return path
 
 
 @dataclasses.dataclass
@@ -95,7 +123,6 @@ class BpeSpec:
     vmask: int = 0
     vpool: Optional[np.ndarray] = None     # uint8: the entries' raw bytes
     vlongest: int = 0                      # bytes of the longest entry
-    added_mask: Optional[np.ndarray] = None  # uint64 [4]: first bytes of the added tokens
     nfc: bool = False                      # the normalizer is NFC: documents it may change come back -2
     # the SentencePiece-style family (kind BPE_SP, csrc/common/bpe_sp.h): byte_id holds the ids of <0xNN>
     sp_prepend: int = 0                    # SP_PREPEND_*: a U+2581 in front of the text
@@ -107,13 +134,13 @@ class BpeSpec:
 
     @property
     def sp_flags(self) -> int:
-        return self.sp_prepend | (4 if self.sp_split else 0)  # bpe_sp.h BpeSpFlags
+        return self.sp_prepend | (SP_SPLIT if self.sp_split else 0)
 
 
 BPE_GPT2, BPE_SPLIT_A, BPE_SPLIT_B, BPE_CASE_C, BPE_CASE_D = 0, 1, 2, 3, 4  # csrc/common/bpe.h BpeKind
 BPE_SP = 5  # SentencePiece-style character-level BPE with byte_fallback (csrc/common/bpe_sp.h)
 SP_SPACE = "▁"  # "▁": what these tokenizers write for U+0020
-SP_PREPEND_NONE, SP_PREPEND_ALWAYS, SP_PREPEND_UNLESS_SPACE = 0, 1, 2  # bpe_sp.h kBpeSpPrepend*
+SP_PREPEND_NONE, SP_PREPEND_ALWAYS, SP_PREPEND_UNLESS_SPACE, SP_SPLIT = 0, 1, 2, 4  # bpe.h BpeSpFlags
 SPLIT_MAX_ADDED, SPLIT_MAX_ADDED_BYTES = 1024, 65536  # kBpeSplitMaxAdded, kBpeSplitMaxAddedBytes
 # the Split patterns counted on the device: Llama-3 / cl100k_base, and the Qwen2 family
 SPLIT_PATTERN_A = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
@@ -247,15 +274,11 @@ def _build_sp_spec(tj: dict, prepend: int, split: bool) -> Optional[BpeSpec]:
     # matched on normalised text: the same statement about the raw text only without a space in it
     if any(t.get("normalized") and (" " in t["content"] or SP_SPACE in t["content"]) for t in toks):
         return None
-    added = [t["content"].encode("utf-8") for t in toks]
-    off = [0]
-    for t in added:
-        off.append(off[-1] + len(t))
-    if len(added) > SPLIT_MAX_ADDED or off[-1] > SPLIT_MAX_ADDED_BYTES:
+    added, off = _pack_added([t["content"] for t in toks])
+    if len(toks) > SPLIT_MAX_ADDED or len(added) > SPLIT_MAX_ADDED_BYTES:
         return None
     h = native.host()
-    u32 = lambda v: np.array(v, dtype=np.uint32)  # noqa: E731
-    keys, vals, mask = h.bpe_build_table(u32(a), u32(b), u32(rank), u32(nid))
+    keys, vals, mask = h.bpe_build_table(_u32(a), _u32(b), _u32(rank), _u32(nid))
     sp_ascii = np.full(128, 0xFFFFFFFF, dtype=np.uint32)
     cps, ids = [], []
     for s, i in vocab.items():
@@ -265,11 +288,9 @@ def _build_sp_spec(tj: dict, prepend: int, split: bool) -> Optional[BpeSpec]:
             else:
                 cps.append(ord(s))
                 ids.append(i)
-    sp_cp, sp_mask = h.bpe_sp_build_table(u32(cps), u32(ids))
-    spec = BpeSpec(u32([vocab[t] for t in byte_tokens]), keys, vals, int(mask),
-                   np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(), off if added else [], post)
+    sp_cp, sp_mask = h.bpe_sp_build_table(_u32(cps), _u32(ids))
+    spec = BpeSpec(_u32([vocab[t] for t in byte_tokens]), keys, vals, int(mask), added, off, post)
     spec.kind = BPE_SP
-    spec.added_mask = h.bpe_added_mask(spec.added, spec.added_off)
     spec.sp_prepend, spec.sp_split = prepend, split
     spec.sp_ascii, spec.sp_cp, spec.sp_mask, spec.sp_id = sp_ascii, sp_cp, int(sp_mask), int(vocab[SP_SPACE])
     return spec
@@ -332,24 +353,19 @@ def build_bpe_spec(tj: dict, nfc: bool = False) -> Optional[BpeSpec]:
     if mg is None:
         return None
     a, b, rank, nid, _ = mg
-    u32 = lambda v: np.array(v, dtype=np.uint32)  # noqa: E731
-    keys, vals, mask = native.host().bpe_build_table(u32(a), u32(b), u32(rank), u32(nid))
-    added = [t["content"].encode("utf-8") for t in tj.get("added_tokens") or [] if t.get("content")]
-    if len(added) > (MAX_ADDED if kind == BPE_GPT2 else SPLIT_MAX_ADDED):
+    keys, vals, mask = native.host().bpe_build_table(_u32(a), _u32(b), _u32(rank), _u32(nid))
+    contents = [t["content"] for t in tj.get("added_tokens") or [] if t.get("content")]
+    if len(contents) > (MAX_ADDED if kind == BPE_GPT2 else SPLIT_MAX_ADDED):
         return None
-    off = [0]
-    for t in added:
-        off.append(off[-1] + len(t))
-    spec = BpeSpec(byte_id, keys, vals, int(mask), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
-                   off if added else [], post)
+    added, off = _pack_added(contents)
+    spec = BpeSpec(byte_id, keys, vals, int(mask), added, off, post)
     if kind == BPE_GPT2:
         return spec
-    if off[-1] > SPLIT_MAX_ADDED_BYTES:
+    if len(added) > SPLIT_MAX_ADDED_BYTES:
         return None
     spec.kind = kind
     spec.nfc = nfc
     spec.ignore_merges = bool(m.get("ignore_merges"))
-    spec.added_mask = native.host().bpe_added_mask(spec.added, spec.added_off)
     if spec.ignore_merges:
         # the vocabulary as raw bytes (entries with a character outside the byte-level alphabet
         # can never equal a pre-token)
@@ -432,17 +448,13 @@ def build_wordpiece_spec(tj: dict, fold: bool = False) -> Optional[WordPieceSpec
     np.cumsum([len(p) for p in pieces], out=off[1:])
     pool = np.frombuffer(b"".join(pieces), dtype=np.uint8).copy()
     slots, mask, longest = native.host().wp_build_table(pool, off, np.array(cont, dtype=np.uint8))
-    added = [t["content"].encode("utf-8") for t in toks]
-    aoff = [0]
-    for t in added:
-        aoff.append(aoff[-1] + len(t))
+    added, aoff = _pack_added([t["content"] for t in toks])
     mode = (1 if lower else 0) | (2 if strip else 0) if fold else 0
     return WordPieceSpec(slots, int(mask), pool, (WP_LOWER if lower else 0) | (WP_CHINESE if nz.get(
         "handle_chinese_chars", True) else 0), 0 if nz.get("clean_text", True) else 2,
         0 if mode else {(False, False): 0, (True, False): 1 << 4, (False, True): 1 << 5,
                         (True, True): 1 << 6}[(lower, strip)],
-        max_chars, int(longest), np.frombuffer(b"".join(added) or b"\0", dtype=np.uint8).copy(),
-        aoff if added else [], post, mode)
+        max_chars, int(longest), added, aoff, post, mode)
 
 
 class TokenCounterModel:
@@ -518,20 +530,7 @@ def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: 
     from .. import native
 
     h = native.host()
-    if isinstance(sp, WordPieceSpec):
-        return h.wp_count(data, off, sp.slots, sp.mask, sp.pool, sp.flags, sp.cls_shift, sp.self_bit, sp.max_chars,
-                          sp.longest, sp.added, sp.added_off, sp.post_add, nthreads, chunk, sp.fold)
-    if sp.kind == BPE_GPT2:
-        return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
-                           nthreads, chunk)
-    none64, none8 = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint8)
-    if sp.kind == BPE_SP:
-        return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
-                           nthreads, chunk, sp.kind, sp_ascii=sp.sp_ascii, sp_cp=sp.sp_cp, sp_mask=sp.sp_mask,
-                           sp_id=sp.sp_id, sp_flags=sp.sp_flags)
-    return h.bpe_count(data, off, sp.byte_id, sp.keys, sp.vals, sp.mask, sp.added, sp.added_off, sp.post_add,
-                       nthreads, chunk, sp.kind, sp.ignore_merges, none64 if sp.vslots is None else sp.vslots,
-                       sp.vmask, none8 if sp.vpool is None else sp.vpool, sp.vlongest, sp.nfc)
+    return (h.wp_count if isinstance(sp, WordPieceSpec) else h.bpe_count)(data, off, sp, nthreads, chunk)
 
 
 def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
@@ -558,11 +557,7 @@ def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 
     tok.post_processor = processors.TemplateProcessing(
         single="[CLS] $A [SEP]", pair="[CLS] $A [SEP] $B:1 [SEP]:1",
         special_tokens=[("[CLS]", tok.token_to_id("[CLS]")), ("[SEP]", tok.token_to_id("[SEP]"))])
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = f"{path}.{os.getpid()}.tmp"
-    tok.save(tmp)
-    os.replace(tmp, path)
-    return path
+    return _save_atomically(path, tok.save)
 
 
 def train_synthetic_bpe(path: str, vocab_size: int = 50257, n_docs: int = 20000, seed: int = 1) -> str:
@@ -585,11 +580,7 @@ def train_synthetic_bpe(path: str, vocab_size: int = 50257, n_docs: int = 20000,
     tr = trainers.BpeTrainer(vocab_size=vocab_size, special_tokens=["<|endoftext|>"], show_progress=False,
                              initial_alphabet=pre_tokenizers.ByteLevel.alphabet())
     tok.train_from_iterator(texts, tr)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = f"{path}.{os.getpid()}.tmp"
-    tok.save(tmp)
-    os.replace(tmp, path)
-    return path
+    return _save_atomically(path, tok.save)
 
 
 def train_synthetic_split_bpe(path: str, vocab_size: int = 32000, pattern: str = "A", ignore_merges: bool = True,
@@ -628,11 +619,7 @@ def train_synthetic_split_bpe(path: str, vocab_size: int = 32000, pattern: str =
             single="<|begin_of_text|> $A", pair="<|begin_of_text|> $A <|begin_of_text|>:1 $B:1",
             special_tokens=[("<|begin_of_text|>", tok.token_to_id("<|begin_of_text|>"))]))
     tok.post_processor = processors.Sequence(procs)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = f"{path}.{os.getpid()}.tmp"
-    tok.save(tmp)
-    os.replace(tmp, path)
-    return path
+    return _save_atomically(path, tok.save)
 
 
 _SP_SPECIAL = ["<unk>", "<s>", "</s>"]
@@ -700,12 +687,11 @@ def train_synthetic_sp_bpe(path: str, vocab_size: int = 32000, layout: str = "L"
         {"type": "Replace", "pattern": {"String": SP_SPACE}, "content": " "}, {"type": "ByteFallback"},
         {"type": "Fuse"}]}
     Tokenizer.from_str(json.dumps(tj))  # the library reads what was written
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = f"{path}.{os.getpid()}.tmp"
-    with open(tmp, "w", encoding="utf-8") as f:
-        json.dump(tj, f, ensure_ascii=False)
-    os.replace(tmp, path)
-    return path
+    def write(tmp):
+        with open(tmp, "w", encoding="utf-8") as f:
+            json.dump(tj, f, ensure_ascii=False)
+
+    return _save_atomically(path, write)
 
 
 def load_tokenizer(name: str, tokenizer_dir: Optional[str] = None) -> TokenCounterModel:

@@ -9,7 +9,9 @@ The argument groups the document kernels share travel as structs (``LAUNCH_STRUC
 mirror of its C struct in csrc/hip/kernel_common.h or its family's unit, sizes checked when
 ``Kernels`` is created): ``Tables`` per batch, ``Docs`` and ``Work`` per launch, ``DictIn`` /
 ``DictLines`` per content version / C4 step. ``_SIGS`` types them as ``POINTER(Struct)``, so a
-struct in the wrong place raises in Python.
+struct in the wrong place raises in Python. The token counters' parameter blocks (DevBpe, DevWp) have
+no mirror here: the host module fills them (csrc/host/tok_params.h) and returns them as bytes, as it
+does the device plan, and ``BpeTables`` / ``WpTables`` only upload the arrays and keep the block.
 """
 from __future__ import annotations
 
@@ -157,115 +159,40 @@ PRE_WCHUNK = 2048  # prepass.hip kPreWChunk
 PRE_TILE = 16384  # prepass.hip kPreTile
 
 
-class DevBpe(ctypes.Structure):
-    """csrc/common/bpe.h DevBpe (checked against tb_sizeof_bpe)."""
-    _fields_ = [("byte_id", _P), ("keys", _P), ("vals", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
-                ("mask", _U32), ("n_added", _I32), ("added_off", _I32 * 9), ("post_add", _I32),
-                ("aoff", _P), ("vslots", _P), ("vpool", _P), ("nfc1", _P), ("nfc2", _P),
-                ("ccls1", _P), ("ccls2", _P),
-                ("amask", ctypes.c_uint64 * 4), ("vmask", _U32), ("vlongest", _I32), ("kind", _I32),
-                ("ignore_merges", _I32), ("nfc", _I32), ("sp_flags", _I32),
-                ("sp_ascii", _P), ("sp_cp", _P), ("sp_mask", _U32), ("sp_id", _U32)]
+class _TokTables:
+    """A token counter's tables in HBM and the kernel's parameter block pointing at them. The block
+    is built by the host module (csrc/host/tok_params.h: the code that fills it for the host
+    emulation too) from the spec and the addresses of ``arrays`` (name -> host array, None = the
+    spec has none); a spec it refuses raises DeviceError."""
 
-
-class BpeTables:
-    """A byte-level BPE tokenizer's tables in HBM (models/tokenizer.py BpeSpec) and the kernel's
-    parameter block pointing at them."""
-
-    def __init__(self, spec, cls_tables, nfc_tables=None, case_tables=None):
+    def __init__(self, params, spec, arrays):
         from . import hiprt
 
-        self.arrays = [hiprt.to_device(a) for a in (spec.byte_id, spec.keys, spec.vals, cls_tables[0], cls_tables[1],
-                                                    spec.added)]
-        split = spec.kind != 0
-        if len(spec.added_off) > (1025 if split else 9):
-            raise DeviceError("bpe: too many added tokens")
-        st = DevBpe()
-        st.byte_id, st.keys, st.vals, st.cls1, st.cls2, st.added = [a.data_ptr() for a in self.arrays]
-        st.mask = spec.mask
-        st.n_added = max(len(spec.added_off) - 1, 0)
-        st.post_add = spec.post_add
-        st.kind = spec.kind
-        if not split:
-            for i, v in enumerate(spec.added_off):
-                st.added_off[i] = v
-        else:
-            # the split-regex family: the added tokens' offsets and the vocabulary table in HBM
-            if spec.added_off and (spec.added_off[-1] > len(spec.added) or spec.added_mask is None):
-                raise DeviceError("bpe: added-token buffers")
-            self.arrays.append(hiprt.to_device(np.array(spec.added_off or [0], dtype=np.int32)))
-            st.aoff = self.arrays[-1].data_ptr()
-            for i in range(4):
-                st.amask[i] = int(spec.added_mask[i]) if spec.added_off else 0
-            if spec.ignore_merges:
-                if spec.vslots is None or len(spec.vslots) != 2 * (spec.vmask + 1) or spec.vlongest < 1:
-                    raise DeviceError("bpe: vocabulary table shape")
-                self.arrays += [hiprt.to_device(spec.vslots), hiprt.to_device(spec.vpool)]
-                st.vslots, st.vpool = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
-                st.vmask, st.vlongest, st.ignore_merges = spec.vmask, spec.vlongest, 1
-        if spec.kind == 5:
-            # the SentencePiece-style family (csrc/common/bpe_sp.h): the single-character entries' ids
-            if (spec.sp_ascii is None or len(spec.sp_ascii) != 128 or spec.sp_cp is None
-                    or len(spec.sp_cp) != spec.sp_mask + 1 or not (spec.sp_cp == np.uint64(2 ** 64 - 1)).any()):
-                raise DeviceError("bpe: code point tables")
-            self.arrays += [hiprt.to_device(spec.sp_ascii), hiprt.to_device(spec.sp_cp)]
-            st.sp_ascii, st.sp_cp = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
-            st.sp_mask, st.sp_id, st.sp_flags = spec.sp_mask, spec.sp_id, spec.sp_flags
-        if spec.kind in (3, 4):
-            # the case-aware patterns' class table (csrc/common/bpe_case_classes.inc)
-            if case_tables is None:
-                raise DeviceError("bpe: the case-aware patterns need their class table")
-            self.arrays += [hiprt.to_device(case_tables[0]), hiprt.to_device(case_tables[1])]
-            st.ccls1, st.ccls2 = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr()
-        if spec.nfc:
-            # the NFC gate's table (csrc/common/nfc_qc.inc)
-            if not split or nfc_tables is None:
-                raise DeviceError("bpe: the NFC gate needs a split-regex spec and its table")
-            self.arrays += [hiprt.to_device(nfc_tables[0]), hiprt.to_device(nfc_tables[1])]
-            st.nfc1, st.nfc2, st.nfc = self.arrays[-2].data_ptr(), self.arrays[-1].data_ptr(), 1
-        self.struct = st
+        self.arrays = {name: hiprt.to_device(a) for name, a in arrays.items() if a is not None}
+        try:
+            self.block = params(spec, {name: a.data_ptr() for name, a in self.arrays.items()})
+        except ValueError as e:
+            raise DeviceError(str(e)) from e
 
 
-class DevWp(ctypes.Structure):
-    """csrc/common/wordpiece.h DevWp (checked against tb_sizeof_wp)."""
-    _fields_ = [("slots", _P), ("pool", _P), ("cls1", _P), ("cls2", _P), ("added", _P),
-                ("fold1", _P), ("fold2", _P), ("foldp", _P),
-                ("asc", ctypes.c_uint64 * 4), ("mask", _U32), ("flags", _U32), ("cls_shift", _U32),
-                ("self_bit", _U32), ("max_chars", _I32), ("longest", _I32), ("post_add", _I32), ("n_added", _I32),
-                ("added_off", _I32 * 9)]
+class BpeTables(_TokTables):
+    """csrc/common/bpe.h DevBpe of a models/tokenizer.py BpeSpec; ``static``: the class / NFC tables
+    of its family by DevBpe field name."""
+
+    def __init__(self, h, spec, static):
+        super().__init__(h.bpe_params, spec, {
+            "byte_id": spec.byte_id, "keys": spec.keys, "vals": spec.vals, "added": spec.added,
+            "aoff": np.array(spec.added_off or [0], dtype=np.int32), "vslots": spec.vslots, "vpool": spec.vpool,
+            "sp_ascii": spec.sp_ascii, "sp_cp": spec.sp_cp, **static})
 
 
-class WpTables:
-    """A WordPiece tokenizer's tables in HBM (models/tokenizer.py WordPieceSpec) and the kernel's
-    parameter block pointing at them."""
+class WpTables(_TokTables):
+    """csrc/common/wordpiece.h DevWp of a models/tokenizer.py WordPieceSpec; ``static``: the class
+    table and, for a folding spec, wp_fold.inc (stage 1 of all three modes: the block names the
+    mode's, and tb_wp_count then launches k_wp_count_fold)."""
 
-    def __init__(self, spec, cls_tables, ascii_classes, fold_tables=None):
-        from . import hiprt
-
-        if len(spec.added_off) > 9:
-            raise DeviceError("wordpiece: too many added tokens")
-        if len(spec.slots) != 2 * (spec.mask + 1) or spec.longest < 1:
-            raise DeviceError("wordpiece: vocabulary table shape")
-        self.arrays = [hiprt.to_device(a) for a in (spec.slots, spec.pool, cls_tables[0], cls_tables[1], spec.added)]
-        st = DevWp()
-        st.slots, st.pool, st.cls1, st.cls2, st.added = [a.data_ptr() for a in self.arrays]
-        if spec.fold:
-            # wp_fold.inc: the stage 1 of the tokenizer's mode, the shared stage 2 and the records
-            # (tb_wp_count then launches k_wp_count_fold)
-            if fold_tables is None or not 1 <= spec.fold <= 3:
-                raise DeviceError("wordpiece: fold tables")
-            f1, f2, fp = fold_tables
-            self.arrays += [hiprt.to_device(np.ascontiguousarray(f1[spec.fold - 1])), hiprt.to_device(f2),
-                            hiprt.to_device(fp)]
-            st.fold1, st.fold2, st.foldp = [a.data_ptr() for a in self.arrays[-3:]]
-        for i in range(4):
-            st.asc[i] = int(ascii_classes[i])
-        st.mask, st.flags, st.cls_shift, st.self_bit = spec.mask, spec.flags, spec.cls_shift, spec.self_bit
-        st.max_chars, st.longest, st.post_add = spec.max_chars, spec.longest, spec.post_add
-        st.n_added = max(len(spec.added_off) - 1, 0)
-        for i, v in enumerate(spec.added_off):
-            st.added_off[i] = v
-        self.struct = st
+    def __init__(self, h, spec, static):
+        super().__init__(h.wp_params, spec, {"slots": spec.slots, "pool": spec.pool, "added": spec.added, **static})
 
 
 def declare(lib: ctypes.CDLL) -> None:
@@ -300,8 +227,9 @@ class Kernels:
         if (self.lib.tb_sizeof_plan() != h.SIZEOF_DEV_PLAN or self.lib.tb_sizeof_stage() != h.SIZEOF_DEV_STAGE
                 or self.lib.tb_sizeof_gate() != h.SIZEOF_DEV_GATE
                 or self.lib.tb_sizeof_resolve() != h.SIZEOF_DEV_RESOLVE
-                or self.lib.tb_sizeof_meta_plan() != h.SIZEOF_DEV_META_PLAN):
-            raise DeviceError("libtbhip.so and _tbhost disagree on the device plan layout; rebuild")
+                or self.lib.tb_sizeof_meta_plan() != h.SIZEOF_DEV_META_PLAN
+                or self.lib.tb_sizeof_bpe() != h.SIZEOF_DEV_BPE or self.lib.tb_sizeof_wp() != h.SIZEOF_DEV_WP):
+            raise DeviceError("libtbhip.so and _tbhost disagree on the device plan or token counter layout; rebuild")
         self.sizeof_gr_export = int(self.lib.tb_sizeof_gr_export())
         if int(self.lib.tb_sizeof_pre_doc()) != PRE_DOC.itemsize:
             raise DeviceError("libtbhip.so and ops/kernels.py disagree on PreDoc; rebuild")
@@ -508,12 +436,15 @@ class Kernels:
 
     def bpe_tables(self, spec) -> BpeTables:
         from .. import native
+        from ..models.tokenizer import BPE_CASE_C, BPE_CASE_D
 
-        if self.lib.tb_sizeof_bpe() != ctypes.sizeof(DevBpe):
-            raise DeviceError("libtbhip.so DevBpe layout differs from the binding; rebuild")
         h = native.host()
-        return BpeTables(spec, h.bpe_classes(), h.nfc_qc() if spec.nfc else None,
-                         h.bpe_case_classes() if spec.kind in (3, 4) else None)
+        static = dict(zip(("cls1", "cls2"), h.bpe_classes()))
+        if spec.kind in (BPE_CASE_C, BPE_CASE_D):  # csrc/common/bpe_case_classes.inc
+            static.update(zip(("ccls1", "ccls2"), h.bpe_case_classes()))
+        if spec.nfc:  # the NFC gate's table (csrc/common/nfc_qc.inc)
+            static.update(zip(("nfc1", "nfc2"), h.nfc_qc()))
+        return BpeTables(h, spec, static)
 
     def bpe_count(self, tabs: BpeTables, text, off, n_dev, n_max: int, counts):
         """k_bpe_count + k_bpe_long, or for a split-regex spec k_bpe_split_count + k_bpe_split_long,
@@ -524,23 +455,24 @@ class Kernels:
         one-element int64 device array (the kept count of K16)."""
         if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
             raise DeviceError("bpe_count: operand shapes")
-        rc = self.lib.tb_bpe_count(self.stream(), ctypes.byref(tabs.struct), text.data_ptr(), off.data_ptr(),
+        rc = self.lib.tb_bpe_count(self.stream(), tabs.block, text.data_ptr(), off.data_ptr(),
                                    _ptr(n_dev), n_max, counts.data_ptr())
         _check(rc, "tb_bpe_count")
 
     def wp_tables(self, spec) -> WpTables:
         from .. import native
 
-        if self.lib.tb_sizeof_wp() != ctypes.sizeof(DevWp):
-            raise DeviceError("libtbhip.so DevWp layout differs from the binding; rebuild")
         h = native.host()
-        return WpTables(spec, h.wp_classes(), h.wp_ascii(spec.cls_shift), h.wp_fold_tables() if spec.fold else None)
+        static = dict(zip(("cls1", "cls2"), h.wp_classes()))
+        if spec.fold:
+            static.update(zip(("fold1", "fold2", "foldp"), h.wp_fold_tables()))
+        return WpTables(h, spec, static)
 
     def wp_count(self, tabs: WpTables, text, off, n_dev, n_max: int, counts):
         """k_wp_count: WordPiece token counts under bpe_count's contract (csrc/hip/wordpiece.hip)."""
         if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
             raise DeviceError("wp_count: operand shapes")
-        rc = self.lib.tb_wp_count(self.stream(), ctypes.byref(tabs.struct), text.data_ptr(), off.data_ptr(),
+        rc = self.lib.tb_wp_count(self.stream(), tabs.block, text.data_ptr(), off.data_ptr(),
                                   _ptr(n_dev), n_max, counts.data_ptr())
         _check(rc, "tb_wp_count")
 

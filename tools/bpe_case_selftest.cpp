@@ -27,83 +27,47 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/common/bpe_case.h"
-#include "../csrc/common/bpe_case_classes.inc"
-#include "../csrc/common/bpe_classes.inc"
-#include "../csrc/common/nfc_qc.inc"
+#include "tok_selftest.h"
 
 using namespace tb;
 
 static int g_fail = 0;
 
 struct Tok {
-  std::vector<uint32_t> byte_id;
-  std::vector<uint64_t> keys, vals;
+  BpeSelfTables tab;
   std::map<std::pair<std::string, std::string>, int> rank;  // the reference's view of the merges
   std::map<std::string, uint32_t> ids;
   std::set<std::string> vocab;
-  std::vector<uint8_t> vpool;
-  std::vector<int64_t> voff{0};
-  std::vector<WpSlot> vslots;
-  std::string added = "<|bot|><eot>";
-  std::vector<int32_t> aoff{0, 7, 12};
   DevBpe T{};
 
   Tok(int kind, bool ignore_merges, bool nfc, const std::vector<std::pair<std::string, std::string>>& merges) {
     for (int i = 0; i < 256; ++i) {
-      byte_id.push_back((uint32_t)i);
+      tab.byte_id.push_back((uint32_t)i);
       ids[std::string(1, (char)i)] = (uint32_t)i;
       vocab.insert(std::string(1, (char)i));
     }
-    size_t cap = 16;
-    while (cap < 2 * merges.size()) cap <<= 1;
-    keys.assign(cap, kBpeEmpty);
-    vals.assign(cap, ~0ull);
+    std::vector<uint32_t> ma, mb, mid;
     for (size_t i = 0; i < merges.size(); ++i) {
       const std::string ab = merges[i].first + merges[i].second;
       const uint32_t next_id = (uint32_t)ids.size();
       if (!ids.count(ab)) ids[ab] = next_id;
       rank[merges[i]] = (int)i;
       vocab.insert(ab);
-      const uint64_t key = ((uint64_t)ids[merges[i].first] << 32) | ids[merges[i].second];
-      uint64_t h = bpe_hash(key) & (cap - 1);
-      while (keys[h] != kBpeEmpty) h = (h + 1) & (cap - 1);
-      keys[h] = key;
-      vals[h] = ((uint64_t)i << 32) | ids[ab];
+      ma.push_back(ids[merges[i].first]);
+      mb.push_back(ids[merges[i].second]);
+      mid.push_back(ids[ab]);
     }
+    tab.set_merges(ma, mb, mid);
     vocab.insert("abc");  // an entry no merge order reaches ("b c" goes first)
     vocab.insert(std::string(70, '-'));  // and one over the lanes' 64-byte arrays
-    std::vector<uint8_t> cont;
-    for (const std::string& w : vocab) {
-      vpool.insert(vpool.end(), w.begin(), w.end());
-      voff.push_back((int64_t)vpool.size());
-      cont.push_back(0);
-    }
-    size_t vcap = 16;
-    while (vcap < 2 * cont.size()) vcap <<= 1;
-    vslots.assign(vcap, WpSlot{0, kWpEmpty});
-    T.vlongest = (int32_t)wp_fill_slots(vpool.data(), voff.data(), cont.data(), cont.size(), vslots.data(), vcap - 1);
-    T.vslots = reinterpret_cast<const uint64_t*>(vslots.data());
-    T.vpool = vpool.data();
-    T.vmask = (uint32_t)(vcap - 1);
-    T.byte_id = byte_id.data();
-    T.keys = keys.data();
-    T.vals = vals.data();
-    T.mask = (uint32_t)(cap - 1);
-    T.cls1 = TB_BPE_CLS_STAGE1;
-    T.cls2 = TB_BPE_CLS_STAGE2;
-    T.ccls1 = TB_BPE_CASE_STAGE1;
-    T.ccls2 = TB_BPE_CASE_STAGE2;
-    T.nfc1 = TB_NFC_QC_STAGE1;
-    T.nfc2 = TB_NFC_QC_STAGE2;
-    T.nfc = nfc;
-    T.added = reinterpret_cast<const uint8_t*>(added.data());
-    T.aoff = aoff.data();
-    T.n_added = 2;
-    bpe_added_mask(T.added, T.aoff, T.n_added, T.amask);
-    T.post_add = 1;
-    T.kind = kind;
-    T.ignore_merges = ignore_merges;
+    tab.set_vocabulary(vocab);
+    tab.added = "<|bot|><eot>";
+    tab.aoff = {0, 7, 12};
+    tab.spec.post_add = 1;
+    tab.spec.kind = kind;
+    tab.spec.ignore_merges = ignore_merges;
+    tab.spec.nfc = nfc;
+    T = tab.params();
   }
 };
 

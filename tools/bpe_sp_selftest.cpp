@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/common/bpe_sp.h"
+#include "tok_selftest.h"
 
 using namespace tb;
 
@@ -40,20 +40,17 @@ static std::string byte_token(uint8_t x) {
 }
 
 struct Tok {
-  std::vector<uint32_t> byte_id, ascii;
-  std::vector<uint64_t> keys, vals, cp;
+  BpeSelfTables tab;
   std::map<std::pair<std::string, std::string>, int> rank;  // the reference's view of the merges
   std::map<std::string, uint32_t> ids;
-  std::string added = "<s></s>";
-  std::vector<int32_t> aoff{0, 3, 7};
   DevBpe T{};
 
   Tok(int flags, const std::vector<std::pair<std::string, std::string>>& merges) {
     for (int i = 0; i < 256; ++i) {
-      byte_id.push_back((uint32_t)i);
+      tab.byte_id.push_back((uint32_t)i);
       ids[byte_token((uint8_t)i)] = (uint32_t)i;
     }
-    ascii.assign(128, kBpeSpNone);
+    tab.sp_ascii.assign(128, kBpeSpNone);
     std::vector<uint32_t> cps, cids;
     // the single characters: é and あ are entries, ü, 日 and the emoji are not; '<' is, 'z' is not
     for (const char* s : {"a", "b", "c", "e", "h", "q", "t", "s", "<", ">", "/", "1", "2", "\n", ".", "\xC3\xA9",
@@ -63,47 +60,35 @@ struct Tok {
       int l;
       const int32_t c = bpe_decode(reinterpret_cast<const uint8_t*>(s), 0, (int64_t)std::strlen(s), &l);
       if (c < 128) {
-        ascii[(size_t)c] = id;
+        tab.sp_ascii[(size_t)c] = id;
       } else if (c == (int32_t)kBpeSpSpace) {
-        T.sp_id = id;
+        tab.spec.sp_id = id;
       } else {
         cps.push_back((uint32_t)c);
         cids.push_back(id);
       }
     }
-    size_t ccap = 16;
-    while (ccap < 2 * cps.size()) ccap <<= 1;
-    cp.resize(ccap);
-    bpe_sp_fill(cps.data(), cids.data(), cps.size(), cp.data(), (uint32_t)(ccap - 1));
-    size_t cap = 16;
-    while (cap < 2 * merges.size()) cap <<= 1;
-    keys.assign(cap, kBpeEmpty);
-    vals.assign(cap, ~0ull);
+    const size_t ccap = tok_table_cap(cps.size());
+    tab.sp_cp.resize(ccap);
+    bpe_sp_fill(cps.data(), cids.data(), cps.size(), tab.sp_cp.data(), (uint32_t)(ccap - 1));
+    tab.spec.sp_mask = (uint32_t)(ccap - 1);
+    std::vector<uint32_t> ma, mb, mid;
     for (size_t i = 0; i < merges.size(); ++i) {
       const std::string ab = merges[i].first + merges[i].second;
       const uint32_t next_id = (uint32_t)ids.size();
       if (!ids.count(ab)) ids[ab] = next_id;
       rank[merges[i]] = (int)i;
-      const uint64_t key = ((uint64_t)ids.at(merges[i].first) << 32) | ids.at(merges[i].second);
-      uint64_t h = bpe_hash(key) & (cap - 1);
-      while (keys[h] != kBpeEmpty) h = (h + 1) & (cap - 1);
-      keys[h] = key;
-      vals[h] = ((uint64_t)i << 32) | ids[ab];
+      ma.push_back(ids.at(merges[i].first));
+      mb.push_back(ids.at(merges[i].second));
+      mid.push_back(ids[ab]);
     }
-    T.byte_id = byte_id.data();
-    T.keys = keys.data();
-    T.vals = vals.data();
-    T.mask = (uint32_t)(cap - 1);
-    T.sp_ascii = ascii.data();
-    T.sp_cp = cp.data();
-    T.sp_mask = (uint32_t)(ccap - 1);
-    T.sp_flags = flags;
-    T.added = reinterpret_cast<const uint8_t*>(added.data());
-    T.aoff = aoff.data();
-    T.n_added = 2;
-    bpe_added_mask(T.added, T.aoff, T.n_added, T.amask);
-    T.post_add = 1;
-    T.kind = kBpeSp;
+    tab.set_merges(ma, mb, mid);
+    tab.spec.sp_flags = flags;
+    tab.added = "<s></s>";
+    tab.aoff = {0, 3, 7};
+    tab.spec.post_add = 1;
+    tab.spec.kind = kBpeSp;
+    T = tab.params();
   }
 };
 

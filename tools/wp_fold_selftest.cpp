@@ -21,54 +21,35 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/common/wordpiece.h"
-#include "../csrc/common/wp_classes.inc"
-#include "../csrc/common/wp_fold.inc"
+#include "tok_selftest.h"
 
 using namespace tb;
 
 static int g_fail = 0;
 
 struct Vocab {
-  std::vector<uint8_t> pool;
+  WpSelfTables tab;
   std::vector<int64_t> off{0};
   std::vector<uint8_t> cont;
-  std::vector<WpSlot> slots;
   std::set<std::pair<int, std::string>> pieces;
-  std::string added = "[CLS][MASK]";
   DevWp T{};
 
   void add(int c, const std::string& s) {
     if (!pieces.insert({c, s}).second) return;
-    pool.insert(pool.end(), s.begin(), s.end());
-    off.push_back((int64_t)pool.size());
+    tab.pool.insert(tab.pool.end(), s.begin(), s.end());
+    off.push_back((int64_t)tab.pool.size());
     cont.push_back((uint8_t)c);
   }
 
   void finish(int fold, int max_chars) {
-    size_t cap = 16;
-    while (cap < 2 * cont.size()) cap <<= 1;
-    slots.assign(cap, WpSlot{0, kWpEmpty});
-    T.longest = (int32_t)wp_fill_slots(pool.data(), off.data(), cont.data(), cont.size(), slots.data(), cap - 1);
-    T.slots = slots.data();
-    T.pool = pool.data();
-    T.cls1 = TB_WP_CLS_STAGE1;
-    T.cls2 = TB_WP_CLS_STAGE2;
-    T.fold1 = TB_WP_FOLD_STAGE1 + (size_t)(fold - 1) * TB_WP_FOLD_NSTAGE1;
-    T.fold2 = TB_WP_FOLD_STAGE2;
-    T.foldp = TB_WP_FOLD_POOL;
-    T.added = reinterpret_cast<const uint8_t*>(added.data());
-    uint64_t a[4];
-    wp_ascii_classes(T.cls1, T.cls2, 0, a);
-    T.asc0 = a[0]; T.asc1 = a[1]; T.asc2 = a[2]; T.asc3 = a[3];
-    T.mask = (uint32_t)(cap - 1);
-    T.flags = kWpChinese | ((fold & 1) ? kWpLower : 0);
-    T.cls_shift = 0;
-    T.self_bit = 0;
-    T.max_chars = max_chars;
-    T.post_add = 2;
-    T.n_added = 2;
-    T.added_off[0] = 0; T.added_off[1] = 5; T.added_off[2] = 11;
+    tab.set_pieces(off, cont);
+    tab.added = "[CLS][MASK]";
+    tab.aoff = {0, 5, 11};
+    tab.spec.fold = fold;
+    tab.spec.flags = kWpChinese | ((fold & 1) ? kWpLower : 0);
+    tab.spec.max_chars = max_chars;
+    tab.spec.post_add = 2;
+    T = tab.params();
   }
 };
 
@@ -213,7 +194,7 @@ int main(int argc, char** argv) {
       V.add(1, w);
     V.finish(fold, 100);
     run(V, names[fold - 1], ndocs, 7 + (uint64_t)fold);
-    V.T.max_chars = 3;
+    V.finish(fold, 3);
     run(V, "3 characters", ndocs / 4, 11 + (uint64_t)fold);
   }
   std::printf("%d failures\n", g_fail);
