@@ -2904,6 +2904,10 @@ TB_HD void c4_pass_a(DocCtx<P>& x, const DevC4& c4, const uint8_t* b, uint32_t n
   });
   x.par.for_n(NLn, [&](uint32_t k) { Pb[poff[k] + plen[k]] = '\n'; });
   x.par.single([&]() { poff[NLn] = Ptot; });
+  // Pb is read next (decode tests its bytes without a barrier of its own): in the workgroup kernel
+  // a wave would otherwise segment bytes another wave has not written yet - whatever the scratch
+  // slice held before - and lose or split the words of a line
+  x.par.sync();
   x.stamp(PH_C4_CITE);
   // ---- words of the processed lines ----
   uint32_t* nw = nullptr;

@@ -1,7 +1,8 @@
 // The token counters' part of _tbhost: table builders, the host emulation of the counting kernels
-// (csrc/common/bpe.h, wordpiece.h; device kernels csrc/hip/bpe.hip, wordpiece.hip) and the kernels'
-// parameter blocks as bytes. Every entry point takes the Python spec object (models/tokenizer.py
-// BpeSpec / WordPieceSpec); tok_params.h validates it and fills the block, here as there.
+// (csrc/common/bpe.h, wordpiece.h, unigram.h; device kernels csrc/hip/bpe.hip, wordpiece.hip,
+// unigram.hip) and the kernels' parameter blocks as bytes. Every entry point takes the Python spec
+// object (models/tokenizer.py BpeSpec / WordPieceSpec / UnigramSpec); tok_params.h validates it and
+// fills the block, here as there.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -10,6 +11,8 @@
 #include <cstring>
 #include <string>
 #include <thread>
+
+#include <unicode/uchar.h>
 
 #include "np_util.h"
 #include "tok_params.h"
@@ -46,6 +49,32 @@ struct WpSpecArrays {
   Arr<uint8_t> pool, added;
   std::vector<int32_t> added_off;
 };
+
+struct UniSpecArrays {
+  Arr<uint64_t> slots;
+  Arr<uint8_t> pool, added, cls2, sp;
+  Arr<uint16_t> cls1;
+  std::vector<int32_t> added_off;
+};
+
+UniSpecView uni_view(const py::object& s, UniSpecArrays& a) {
+  UniSpecView v;
+  v.slots = spec_array(s, "slots", a.slots);
+  v.pool = spec_array(s, "pool", a.pool);
+  v.added = spec_array(s, "added", a.added);
+  v.cls1 = spec_array(s, "cls1", a.cls1);
+  v.cls2 = spec_array(s, "cls2", a.cls2);
+  v.sp = spec_array(s, "sp", a.sp);
+  a.added_off = s.attr("added_off").cast<std::vector<int32_t>>();
+  v.added_off = {a.added_off.data(), a.added_off.size()};
+  v.mask = s.attr("mask").cast<uint32_t>();
+  v.flags = s.attr("flags").cast<uint32_t>();
+  v.longest_cp = s.attr("longest_cp").cast<int32_t>();
+  v.longest = s.attr("longest").cast<int32_t>();
+  v.post_add = s.attr("post_add").cast<int32_t>();
+  v.unk_score = s.attr("unk_score").cast<double>();
+  return v;
+}
 
 BpeSpecView bpe_view(const py::object& s, BpeSpecArrays& a) {
   BpeSpecView v;
@@ -152,6 +181,20 @@ void register_tok(py::module_& m) {
     c["SP_PREPEND_ALWAYS"] = (int)kBpeSpPrependAlways; c["SP_PREPEND_UNLESS_SPACE"] = (int)kBpeSpPrependUnlessSpace;
     c["SP_SPLIT"] = (int)kBpeSpSplit; c["WP_LOWER"] = kWpLower; c["WP_CHINESE"] = kWpChinese;
     m.attr("TOK_CONSTANTS") = c;
+    py::dict u, uc;
+#define TB_OFF(d, S, f) d[#f] = offsetof(S, f)
+    TB_OFF(u, DevUni, slots); TB_OFF(u, DevUni, pool); TB_OFF(u, DevUni, cls1); TB_OFF(u, DevUni, cls2);
+    TB_OFF(u, DevUni, added); TB_OFF(u, DevUni, aoff); TB_OFF(u, DevUni, asc0); TB_OFF(u, DevUni, asc1);
+    TB_OFF(u, DevUni, asc2); TB_OFF(u, DevUni, asc3); TB_OFF(u, DevUni, amask); TB_OFF(u, DevUni, unk_score);
+    TB_OFF(u, DevUni, mask); TB_OFF(u, DevUni, flags); TB_OFF(u, DevUni, sp_bytes); TB_OFF(u, DevUni, sp_len);
+    TB_OFF(u, DevUni, longest_cp); TB_OFF(u, DevUni, longest); TB_OFF(u, DevUni, post_add); TB_OFF(u, DevUni, n_added);
+#undef TB_OFF
+    m.attr("DEV_UNI_OFFSETS") = u;
+    m.attr("SIZEOF_DEV_UNI") = sizeof(DevUni);
+    uc["UNI_KEEP"] = (int)UNI_KEEP; uc["UNI_SPACE"] = (int)UNI_SPACE; uc["UNI_HOST"] = (int)UNI_HOST;
+    uc["UNI_BYTE_FALLBACK"] = kUniByteFallback; uc["UNI_MAX_PIECE_CP"] = kUniMaxPieceCp;
+    uc["UNI_MAX_PIECE_BYTES"] = kUniMaxPieceBytes;
+    m.attr("UNI_CONSTANTS") = uc;
   }
   // ---- byte-level BPE token counting (csrc/common/bpe.h; device kernel csrc/hip/bpe.hip) ----
   m.def("bpe_classes", []() {
@@ -377,5 +420,84 @@ void register_tok(py::module_& m) {
     addr(ptrs, "fold2", p.fold2); addr(ptrs, "foldp", p.foldp);
     const DevWp T = wp_fill_params(view, p);
     return block_bytes(T, offsetof(DevWp, added_off) + sizeof T.added_off);
+  }, py::arg("spec"), py::arg("ptrs"));
+  // ---- Unigram token counting (csrc/common/unigram.h; device kernel csrc/hip/unigram.hip) ----
+  m.def("uni_grapheme_joiners", []() {
+    // one byte per code point: 1 when its Grapheme_Cluster_Break (ICU) is Extend, ZWJ, SpacingMark,
+    // Prepend, L, V or T - the code points that can share a grapheme with a neighbour other than
+    // CR LF, which the Precompiled normalizer maps as a whole
+    std::vector<uint8_t> out(0x110000, 0);
+    for (UChar32 c = 0; c < 0x110000; ++c) {
+      const int32_t g = u_getIntPropertyValue(c, UCHAR_GRAPHEME_CLUSTER_BREAK);
+      out[(size_t)c] = g == U_GCB_EXTEND || g == U_GCB_ZWJ || g == U_GCB_SPACING_MARK || g == U_GCB_PREPEND ||
+                       g == U_GCB_L || g == U_GCB_V || g == U_GCB_T;
+    }
+    return to_numpy(std::move(out));
+  });
+  m.def("uni_build_table", [](Arr<uint8_t> pool, Arr<int64_t> off, Arr<double> score, int64_t unk) {
+    // pieces i = pool[off[i]:off[i + 1]] of score[i], distinct; open addressing, load <= 1/2.
+    // Returns the slots as uint64 triples (UniSlot) and the mask.
+    const size_t n = (size_t)score.size();
+    if ((size_t)off.size() != n + 1 || n >= (1u << 30)) throw std::invalid_argument("uni_build_table: off needs one entry more than score");
+    const int64_t* o = off.data();
+    for (size_t i = 0; i < n; ++i)
+      if (o[i] < 0 || o[i + 1] <= o[i] || o[i + 1] > pool.size() || o[i + 1] - o[i] >= (1ll << 31) || o[i] >= (1ll << 32))
+        throw std::invalid_argument("uni_build_table: piece offsets");
+    const size_t cap = tok_table_cap(n);
+    std::vector<uint64_t> slots(3 * cap, kWpEmpty);
+    uni_fill_slots(pool.data(), o, score.data(), n, unk < 0 ? n : (size_t)unk, reinterpret_cast<UniSlot*>(slots.data()),
+                   cap - 1);
+    return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)(cap - 1));
+  });
+  m.def("uni_count", [](Arr<uint8_t> data, Arr<int64_t> off, py::object spec, int nthreads, int64_t chunk) {
+    // host emulation of k_uni_count: per document the token count, or kBpeHost. chunk > 0: the wave
+    // split - the words starting in each chunk-byte range counted independently (uni_count_range),
+    // as the kernel's lanes do
+    UniSpecArrays arrays;
+    const UniSpecView view = uni_view(spec, arrays);
+    const DevUni T = uni_fill_params(view, uni_host_ptrs(view));
+    const int64_t nd = off.size() - 1;
+    std::vector<int32_t> out(nd > 0 ? nd : 0);
+    const uint8_t* d = data.data();
+    const int64_t* o = off.data();
+    {
+      py::gil_scoped_release nogil;
+      const int nt = count_threads(nthreads, nd);
+      std::vector<std::thread> th;
+      for (int t = 0; t < nt; ++t)
+        th.emplace_back([&, t]() {
+          double rs[kUniMaxPieceCp + 1];
+          uint32_t rm[kUniMaxPieceCp + 1];
+          const UniRing R{rs, rm, 1};
+          for (int64_t k = t; k < nd; k += nt) {
+            const uint8_t* b = d + o[k];
+            const int64_t n = o[k + 1] - o[k];
+            if (chunk <= 0) {
+              out[k] = uni_count_doc(T, b, n, R);
+              continue;
+            }
+            int64_t tot = T.post_add;
+            bool bad = T.n_added && uni_has_added(T, b, n, 0, n);
+            for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
+              const int64_t x = uni_count_range(T, b, n, s0, std::min(n, s0 + chunk), R);
+              if (x < 0) bad = true;
+              tot += x;
+            }
+            out[k] = (bad || tot > 0x7FFFFFFF) ? kBpeHost : (int32_t)tot;
+          }
+        });
+      for (auto& x : th) x.join();
+    }
+    return to_numpy(std::move(out));
+  }, py::arg("data"), py::arg("off"), py::arg("spec"), py::arg("nthreads") = 8, py::arg("chunk") = 0);
+  m.def("uni_params", [](py::object spec, py::dict ptrs) {
+    // DevUni for the kernel (as bpe_params; the spec's added_off as "aoff")
+    UniSpecArrays arrays;
+    const UniSpecView view = uni_view(spec, arrays);
+    UniPtrs p;
+    addr(ptrs, "slots", p.slots); addr(ptrs, "pool", p.pool); addr(ptrs, "added", p.added);
+    addr(ptrs, "cls1", p.cls1); addr(ptrs, "cls2", p.cls2); addr(ptrs, "aoff", p.aoff);
+    const DevUni T = uni_fill_params(view, p);
+    return block_bytes(T, offsetof(DevUni, n_added) + sizeof T.n_added);
   }, py::arg("spec"), py::arg("ptrs"));
 }

@@ -1,17 +1,20 @@
-// The token counters' parameter blocks (csrc/common/bpe.h DevBpe, csrc/common/wordpiece.h DevWp):
-// the one list of conditions a tokenizer spec must meet (bpe_spec_error / wp_spec_error) and the
-// one place that writes the blocks' fields (bpe_fill_params / wp_fill_params), for both executions:
-// with host addresses the block drives the host emulation (tok_module.cpp bpe_count / wp_count,
-// tools/*_selftest.cpp), with HBM addresses the kernels (tok_module.cpp bpe_params / wp_params,
-// uploaded by ops/kernels.py). No pybind here: the selftests include this file by relative path.
+// The token counters' parameter blocks (csrc/common/bpe.h DevBpe, csrc/common/wordpiece.h DevWp,
+// csrc/common/unigram.h DevUni): the one list of conditions a tokenizer spec must meet
+// (bpe_spec_error / wp_spec_error / uni_spec_error) and the one place that writes the blocks' fields
+// (bpe_fill_params / wp_fill_params / uni_fill_params), for both executions: with host addresses
+// the block drives the host emulation (tok_module.cpp bpe_count / wp_count / uni_count,
+// tools/*_selftest.cpp), with HBM addresses the kernels (tok_module.cpp bpe_params / wp_params /
+// uni_params, uploaded by ops/kernels.py). No pybind here: the selftests include this file by relative path.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
 
 #include "../common/bpe_case.h"
 #include "../common/bpe_sp.h"
+#include "../common/unigram.h"
 #include "../common/bpe_classes.inc"
 #include "../common/bpe_case_classes.inc"
 #include "../common/nfc_qc.inc"
@@ -56,6 +59,16 @@ struct WpSpecView {
   int32_t fold = 0;  // wp_fold.inc: 0 none, 1 lowercase, 2 strip_accents, 3 both
 };
 
+struct UniSpecView {
+  TokSpan<uint64_t> slots;  // UniSlot triples
+  TokSpan<uint8_t> pool, added, cls2, sp;
+  TokSpan<uint16_t> cls1;
+  TokSpan<int32_t> added_off;
+  uint32_t mask = 0, flags = 0;
+  int32_t longest_cp = 0, longest = 0, post_add = 0;
+  double unk_score = 0;
+};
+
 // ---- where the arrays a block points to are: in host memory, or in HBM ----
 struct BpePtrs {
   const uint32_t* byte_id = nullptr;
@@ -81,6 +94,13 @@ struct WpPtrs {
   const uint16_t* fold1 = nullptr;  // wp_fold.inc: stage 1 of all three modes, [3][TB_WP_FOLD_NSTAGE1]
   const uint16_t* fold2 = nullptr;
   const uint8_t* foldp = nullptr;
+};
+
+struct UniPtrs {
+  const uint64_t* slots = nullptr;
+  const uint8_t *pool = nullptr, *added = nullptr, *cls2 = nullptr;
+  const uint16_t* cls1 = nullptr;
+  const int32_t* aoff = nullptr;
 };
 
 // the static tables in host memory
@@ -120,6 +140,17 @@ inline WpPtrs wp_host_ptrs(const WpSpecView& v) {
   p.fold1 = TB_WP_FOLD_STAGE1;
   p.fold2 = TB_WP_FOLD_STAGE2;
   p.foldp = TB_WP_FOLD_POOL;
+  return p;
+}
+
+inline UniPtrs uni_host_ptrs(const UniSpecView& v) {
+  UniPtrs p;
+  p.slots = v.slots.p;
+  p.pool = v.pool.p;
+  p.added = v.added.p;
+  p.cls1 = v.cls1.p;
+  p.cls2 = v.cls2.p;
+  p.aoff = v.added_off.p;
   return p;
 }
 
@@ -171,6 +202,35 @@ inline const char* wp_spec_error(const WpSpecView& v) {
   if (v.cls_shift != 0 && v.cls_shift != 2) return "wordpiece: cls_shift is 0 or 2";
   if (v.max_chars < 0) return "wordpiece: max_chars";
   if (v.fold < 0 || v.fold > 3) return "wordpiece: fold is 0 to 3";
+  return nullptr;
+}
+
+constexpr size_t kUniClsStage1 = 0x110000 >> 7;  // entries of UniSpecView::cls1
+
+inline const char* uni_spec_error(const UniSpecView& v) {
+  static_assert(sizeof(UniSlot) == 24, "UniSlot is three uint64");
+  const size_t cap = (size_t)v.mask + 1;
+  if ((cap & v.mask) != 0 || v.slots.n != 3 * cap) return "unigram: vocabulary table shape";
+  if (v.longest_cp < 1 || v.longest_cp > kUniMaxPieceCp || v.longest < 1 || v.longest > kUniMaxPieceBytes)
+    return "unigram: the longest piece exceeds the ring";
+  size_t free_slots = 0;
+  for (size_t i = 0; i < cap; ++i) {  // every listed piece lies in the pool and fits the longest
+    const uint64_t e = v.slots.p[3 * i + 1];
+    if (e == kWpEmpty) {
+      ++free_slots;
+      continue;
+    }
+    const uint64_t nb = (uint32_t)e & 0x7FFFFFFFu;
+    if (nb < 1 || nb > (uint64_t)v.longest || (e >> 32) + nb > (uint64_t)v.pool.n) return "unigram: a piece lies past the pool";
+  }
+  if (free_slots == 0) return "unigram: the vocabulary table has no free slot";
+  if (v.cls1.n != kUniClsStage1) return "unigram: cls1 needs one entry per 128 code points";
+  for (size_t i = 0; i < v.cls1.n; ++i)
+    if (((size_t)v.cls1.p[i] + 1) * 32 > v.cls2.n) return "unigram: a class block lies past cls2";
+  if (const char* e = tok_added_error(v.added, v.added_off, kBpeSplitMaxAdded, kBpeSplitMaxAddedBytes)) return e;
+  if (v.sp.n < 1 || v.sp.n > 4) return "unigram: the replacement character has 1 to 4 bytes";
+  if (v.flags & ~kUniByteFallback) return "unigram: flags";
+  if (!std::isfinite(v.unk_score)) return "unigram: unk_score";
   return nullptr;
 }
 
@@ -240,6 +300,33 @@ inline DevWp wp_fill_params(const WpSpecView& v, const WpPtrs& p) {
   T.n_added = v.added_off.n ? (int32_t)v.added_off.n - 1 : 0;
   std::copy(v.added_off.p, v.added_off.p + v.added_off.n, T.added_off);
   if (!wp_params_ok(T)) throw std::invalid_argument("wordpiece: a table the tokenizer's mode reads has no address");
+  return T;
+}
+
+inline DevUni uni_fill_params(const UniSpecView& v, const UniPtrs& p) {
+  if (const char* e = uni_spec_error(v)) throw std::invalid_argument(e);
+  DevUni T{};
+  T.slots = reinterpret_cast<const UniSlot*>(p.slots);
+  T.pool = p.pool;
+  T.cls1 = p.cls1;
+  T.cls2 = p.cls2;
+  T.added = p.added;
+  T.aoff = p.aoff;
+  uint64_t asc[4] = {0, 0, 0, 0};  // the ASCII classes, from the view's table (host memory)
+  for (uint32_t c = 0; c < 128; ++c)
+    asc[c >> 5] |= (uint64_t)((v.cls2.p[(size_t)v.cls1.p[0] * 32 + (c >> 2)] >> (2 * (c & 3))) & 3) << (2 * (c & 31));
+  T.asc0 = asc[0]; T.asc1 = asc[1]; T.asc2 = asc[2]; T.asc3 = asc[3];
+  T.n_added = v.added_off.n ? (int32_t)v.added_off.n - 1 : 0;
+  bpe_added_mask(v.added.p, v.added_off.p, T.n_added, T.amask);
+  T.unk_score = v.unk_score;
+  T.mask = v.mask;
+  T.flags = v.flags;
+  for (size_t j = 0; j < v.sp.n; ++j) T.sp_bytes |= (uint32_t)v.sp.p[j] << (8 * j);
+  T.sp_len = (int32_t)v.sp.n;
+  T.longest_cp = v.longest_cp;
+  T.longest = v.longest;
+  T.post_add = v.post_add;
+  if (!uni_params_ok(T)) throw std::invalid_argument("unigram: a table the counter reads has no address");
   return T;
 }
 

@@ -27,9 +27,14 @@ The SentencePiece-converted character-level BPE files with ``byte_fallback`` (Ll
 normalizer Prepend + Replace(" ", "▁") and no pre-tokenizer, or a Metaspace pre-tokenizer) get a
 :class:`BpeSpec` of kind ``BPE_SP`` (csrc/common/bpe_sp.h, k_bpe_sp_count): the ids of the
 single-character entries, of the 256 ``<0xNN>`` tokens and of ``▁``, and the prepend and split rules.
+Unigram files (T5, mT5, XLM-R: a Precompiled normalizer, white-space splitting and Metaspace in one
+of two layouts) get a :class:`UnigramSpec` (:meth:`TokenCounterModel.unigram_spec`; csrc/common/unigram.h,
+k_uni_count): the pieces with their scores in a hash table over a byte pool, and a class table probed
+from the file's own normalizer that says which code points it keeps, turns into a space, or changes
+(documents with one of those are counted by ``tokenizers``).
 
 A spec is data only. The host module reads it as it stands (``bpe_count`` / ``wp_count`` for the host
-emulation, ``bpe_params`` / ``wp_params`` for the kernels' parameter block), and one validator and
+emulation (``uni_count`` for Unigram), ``bpe_params`` / ``wp_params`` / ``uni_params`` for the kernels' parameter block), and one validator and
 one filler there (csrc/host/tok_params.h) decide whether it is usable and write the block for both.
 """
 from __future__ import annotations
@@ -457,6 +462,239 @@ def build_wordpiece_spec(tj: dict, fold: bool = False) -> Optional[WordPieceSpec
         max_chars, int(longest), added, aoff, post, mode)
 
 
+@dataclasses.dataclass
+class UnigramSpec:
+    """Device tables of a Unigram tokenizer (csrc/common/unigram.h DevUni)."""
+    slots: np.ndarray      # uint64 [3 * (mask + 1)]: (key, value, f64 score bits) triples
+    mask: int
+    pool: np.ndarray       # uint8: piece bytes
+    cls1: np.ndarray       # uint16 [0x110000 >> 7]: class table of this file's normalizer, stage 1
+    cls2: np.ndarray       # uint8: stage 2, 32 bytes per block of 128 code points, 2 bits each
+    sp: np.ndarray         # uint8: UTF-8 of the replacement character
+    flags: int             # UNI_BYTE_FALLBACK
+    unk_score: float       # min(score) - 10
+    longest_cp: int        # code points of the longest piece
+    longest: int           # bytes of the longest piece
+    added: np.ndarray      # uint8: added-token contents and the unk piece's text, concatenated
+    added_off: List[int]   # [n_added + 1]
+    post_add: int          # tokens the post-processor adds
+    layout: str = "H"      # "H" (hub files) or "C" (converted files): see build_unigram_spec
+
+
+# csrc/common/unigram.h (pinned to the header's values by tests/test_unigram.py through UNI_CONSTANTS)
+UNI_KEEP, UNI_SPACE, UNI_HOST = 0, 1, 2
+UNI_BYTE_FALLBACK = 1
+UNI_MAX_PIECE_CP, UNI_MAX_PIECE_BYTES = 32, 128
+# Rust's char::is_whitespace (White_Space): what WhitespaceSplit separates on and Strip removes
+RUST_WHITESPACE = frozenset([*range(9, 14), 0x20, 0x85, 0xA0, 0x1680, *range(0x2000, 0x200B), 0x2028, 0x2029, 0x202F,
+                             0x205F, 0x3000])
+_UNI_SQUEEZE = {"Regex": " {2,}"}
+_UNI_JOINERS = r"[\p{GCB=Extend}\p{GCB=ZWJ}\p{GCB=SpacingMark}\p{GCB=Prepend}\p{GCB=L}\p{GCB=V}\p{GCB=T}]"
+
+
+def _metaspace(pt, schemes) -> bool:
+    """Is ``pt`` Metaspace("▁", a prepend scheme of ``schemes``, split true), in today's or the older
+    serialisation (add_prefix_space)?"""
+    if not isinstance(pt, dict) or pt.get("type") != "Metaspace" or pt.get("replacement") != SP_SPACE:
+        return False
+    if set(pt) - {"type", "replacement", "prepend_scheme", "split", "add_prefix_space", "str_rep"}:
+        return False
+    if pt.get("str_rep", SP_SPACE) != SP_SPACE or pt.get("add_prefix_space", True) is not True:
+        return False
+    return pt.get("prepend_scheme", "always") in schemes and pt.get("split", True) is True
+
+
+def _unigram_layout(tj: dict):
+    """(layout, charsmap as base64 or None) when normalizer and pre-tokenizer are one of the two
+    layouts of :func:`build_unigram_spec`, else None."""
+    nz, pt = tj.get("normalizer"), tj.get("pre_tokenizer")
+    if not isinstance(nz, dict) or nz.get("type") != "Sequence" or not isinstance(pt, dict):
+        return None
+    seq = list(nz.get("normalizers") or [])
+    charsmap = None
+    if seq and isinstance(seq[0], dict) and seq[0].get("type") == "Precompiled":
+        charsmap = seq.pop(0).get("precompiled_charsmap")
+        if not isinstance(charsmap, str) or not charsmap:
+            return None
+    if seq == [{"type": "Replace", "pattern": _UNI_SQUEEZE, "content": " "}]:
+        pts = pt.get("pretokenizers") or []
+        if (pt.get("type") == "Sequence" and len(pts) == 2 and pts[0] == {"type": "WhitespaceSplit"}
+                and _metaspace(pts[1], ("always",))):
+            return "H", charsmap
+        return None
+    if seq == [{"type": "Strip", "strip_left": False, "strip_right": True},
+               {"type": "Replace", "pattern": _UNI_SQUEEZE, "content": SP_SPACE}]:
+        # "first" is "always" here: a document with an added token's text, the only kind the library
+        # cuts into sections, goes to the host
+        return ("C", charsmap) if _metaspace(pt, ("always", "first")) else None
+    return None
+
+
+def _two_stage_2bit(cls: np.ndarray):
+    """A class per code point (uint8 [0x110000], values 0..3) as DevUni's two-stage table."""
+    packed = cls.reshape(-1, 4)
+    packed = (packed[:, 0] | (packed[:, 1] << 2) | (packed[:, 2] << 4) | (packed[:, 3] << 6)).astype(np.uint8)
+    blocks, inverse = np.unique(packed.reshape(-1, 32), axis=0, return_inverse=True)
+    return inverse.reshape(-1).astype(np.uint16), np.ascontiguousarray(blocks.reshape(-1))
+
+
+def unigram_probe(charsmap: Optional[str]) -> List[Optional[str]]:
+    """What the file's Precompiled normalizer makes of every scalar value on its own (None for the
+    surrogates); without a charsmap every code point normalises to itself."""
+    if charsmap is None:
+        return [None if 0xD800 <= c < 0xE000 else chr(c) for c in range(0x110000)]
+    import base64
+
+    from tokenizers import normalizers
+
+    f = normalizers.Precompiled(base64.b64decode(charsmap)).normalize_str
+    return [None if 0xD800 <= c < 0xE000 else f(chr(c)) for c in range(0x110000)]
+
+
+def unigram_classes(charsmap: Optional[str], layout: str) -> np.ndarray:
+    """UNI_KEEP / UNI_SPACE / UNI_HOST of every code point for a normalizer and a layout (about 1 s).
+
+    keep: the normalizer leaves the code point as it is. space: it becomes exactly U+0020, it is
+    U+0020, or (layout H) it is kept white space, which WhitespaceSplit separates on. host: the
+    rest - dropped or replaced code points, kept white space in layout C (Strip and embedded white
+    space are no spaces there), a kept U+2581, and behind Precompiled every code point that can
+    share a grapheme with a neighbour (Grapheme_Cluster_Break Extend, ZWJ, SpacingMark, Prepend, L,
+    V, T; the combining marks and unassigned code points of Python's own Unicode data): Precompiled looks a whole grapheme
+    under 6 bytes up and replaces all of it by the shortest matching prefix's output."""
+    import unicodedata
+
+    from .. import native
+
+    out = unigram_probe(charsmap)
+    cls = np.full(0x110000, UNI_HOST, dtype=np.uint8)
+    for c, o in enumerate(out):
+        if o == " " or c == 0x20:
+            cls[c] = UNI_SPACE
+        elif o is not None and o == chr(c) and c != 0x2581:
+            if c in RUST_WHITESPACE:
+                cls[c] = UNI_SPACE if layout == "H" else UNI_HOST
+            else:
+                cls[c] = UNI_KEEP
+    if charsmap is not None:
+        # the library's segmentation may know a newer Unicode than any one source here: the union of
+        # ICU's property, Python's combining marks and unassigned code points, and the regex
+        # module's property where it is installed
+        joiner = native.host().uni_grapheme_joiners().astype(bool)
+        for c in range(0x80, 0x110000):
+            if unicodedata.category(chr(c)) in ("Mn", "Me", "Mc", "Cn"):
+                joiner[c] = True
+        try:
+            import regex
+        except ImportError:
+            regex = None
+        if regex is not None:
+            text = "".join(chr(c) for c in range(0x110000) if not 0xD800 <= c < 0xE000)
+            for hit in regex.finditer(_UNI_JOINERS, text):
+                joiner[ord(hit.group())] = True
+        cls[joiner & (cls == UNI_KEEP)] = UNI_HOST
+    return cls
+
+
+def _unigram_class_table(charsmap: Optional[str], layout: str, cache_dir: Optional[str]):
+    """The two-stage class table, from the cache file next to the tokenizer when there is one."""
+    import hashlib
+
+    key = hashlib.sha256(f"v2:{layout}:{charsmap or ''}".encode("utf-8")).hexdigest()[:16]
+    path = os.path.join(cache_dir, f"unigram_classes.{key}.npz") if cache_dir else None
+    if path and os.path.isfile(path):
+        try:
+            with np.load(path) as z:
+                c1, c2 = z["cls1"].astype(np.uint16), z["cls2"].astype(np.uint8)
+            if c1.shape == (0x110000 >> 7,) and c2.ndim == 1 and (int(c1.max()) + 1) * 32 <= len(c2):
+                return c1, c2
+        except (OSError, ValueError, KeyError):
+            pass
+    c1, c2 = _two_stage_2bit(unigram_classes(charsmap, layout))
+    if path:
+        def write(tmp):
+            with open(tmp, "wb") as f:
+                np.savez_compressed(f, cls1=c1, cls2=c2)
+
+        try:
+            _save_atomically(path, write)
+        except OSError:
+            pass  # a read-only tokenizer directory: probed again next time
+    return c1, c2
+
+
+def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None) -> Optional[UnigramSpec]:
+    """UnigramSpec of a parsed tokenizer.json, or None when the tokenizer is not a Unigram model the
+    device counter reproduces exactly: ``unk_id`` set, no duplicate pieces, finite scores, with
+    ``byte_fallback`` all 256 ``<0xNN>`` pieces, no truncation / padding, a known post-processor, at
+    most SPLIT_MAX_ADDED added tokens of SPLIT_MAX_ADDED_BYTES bytes in all, none matched on
+    normalised text, no piece over UNI_MAX_PIECE_CP code points / UNI_MAX_PIECE_BYTES bytes, and
+    normalizer and pre-tokenizer in one of two layouts:
+
+    * H (the hub files of T5 / mT5 / XLM-R): normalizer Sequence[Precompiled?, Replace(Regex " {2,}" -> " ")],
+      pre-tokenizer Sequence[WhitespaceSplit, Metaspace("▁", prepend always)];
+    * C (what transformers' SpmConverter writes): normalizer Sequence[Precompiled?, Strip(right),
+      Replace(Regex " {2,}" -> "▁")], pre-tokenizer Metaspace("▁", prepend always or first, split).
+
+    In both the count of a document is the sum over its words, each encoded as "▁" + word. The
+    class table comes from probing the file's own Precompiled normalizer (:func:`unigram_classes`)
+    and is cached in ``cache_dir``."""
+    import math
+
+    from .. import native
+
+    m = tj.get("model") or {}
+    if m.get("type") != "Unigram" or tj.get("truncation") is not None or tj.get("padding") is not None:
+        return None
+    lay = _unigram_layout(tj)
+    post = _post_add(tj.get("post_processor"))
+    vocab, unk_id = m.get("vocab"), m.get("unk_id")
+    if lay is None or post is None or not isinstance(vocab, list) or not vocab:
+        return None
+    if not isinstance(unk_id, int) or isinstance(unk_id, bool) or not 0 <= unk_id < len(vocab):
+        return None
+    try:
+        pieces = [p.encode("utf-8") for p, _ in vocab]
+        scores = np.array([float(s) for _, s in vocab], dtype=np.float64)
+    except (TypeError, ValueError, AttributeError, UnicodeEncodeError):
+        return None
+    if len(set(pieces)) != len(pieces) or b"" in pieces or not np.isfinite(scores).all():
+        return None
+    unk_score = float(scores.min()) - 10.0
+    # a run of unknowns must lose against any piece that spells it (else byte_fallback would see a
+    # known string): k (min - 10) < min for every k >= 2
+    if not unk_score < 0.0:
+        return None
+    byte_fallback = bool(m.get("byte_fallback", False))
+    if byte_fallback and not {f"<0x{b:02X}>".encode() for b in range(256)} <= set(pieces):
+        return None
+    longest = max(len(p) for p in pieces)
+    longest_cp = max(len(p) for p, _ in vocab)
+    if longest_cp > UNI_MAX_PIECE_CP or longest > UNI_MAX_PIECE_BYTES:
+        return None
+    toks = [t for t in tj.get("added_tokens") or [] if t.get("content")]
+    if any(t.get("normalized") for t in toks):
+        return None
+    contents = [t["content"] for t in toks]
+    if vocab[unk_id][0] not in contents:  # the unk piece's own text: one more added-token string
+        contents.append(vocab[unk_id][0])
+    added, aoff = _pack_added(contents)
+    if len(contents) > SPLIT_MAX_ADDED or len(added) > SPLIT_MAX_ADDED_BYTES:
+        return None
+    layout, charsmap = lay
+    try:
+        cls1, cls2 = _unigram_class_table(charsmap, layout, cache_dir)
+    except Exception:  # noqa: BLE001 - a charsmap the library does not read
+        return None
+    off = np.zeros(len(pieces) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in pieces], out=off[1:])
+    pool = np.frombuffer(b"".join(pieces), dtype=np.uint8).copy()
+    slots, mask = native.host().uni_build_table(pool, off, scores, unk_id)
+    assert math.isfinite(unk_score)
+    return UnigramSpec(slots, int(mask), pool, cls1, cls2, np.frombuffer(SP_SPACE.encode("utf-8"), dtype=np.uint8).copy(),
+                       UNI_BYTE_FALLBACK if byte_fallback else 0, unk_score, longest_cp, longest, added, aoff, post,
+                       layout)
+
+
 class TokenCounterModel:
     def __init__(self, path: str):
         from tokenizers import Tokenizer
@@ -466,6 +704,7 @@ class TokenCounterModel:
         self._spec = False
         self._wp_spec = False
         self._wp_fold_spec = False
+        self._uni_spec = False
 
     def count(self, texts: List[str]) -> List[int]:
         if not texts:
@@ -500,23 +739,32 @@ class TokenCounterModel:
                     self._wp_fold_spec = build_wordpiece_spec(json.load(f), fold=True)
         return self._wp_fold_spec
 
+    def unigram_spec(self) -> Optional[UnigramSpec]:
+        """Device/native tables when this is a Unigram tokenizer in one of the counted layouts (else
+        None); built once, its class table cached next to the tokenizer file."""
+        if self._uni_spec is False:
+            with open(self.path, encoding="utf-8") as f:
+                self._uni_spec = build_unigram_spec(json.load(f), os.path.dirname(os.path.abspath(self.path)))
+        return self._uni_spec
+
     def device_spec(self):
         """The spec the device path counts with: :class:`BpeSpec`, :class:`WordPieceSpec` (folding
-        when the tokenizer lowercases or strips accents) or None."""
-        return self.bpe_spec() or self.wordpiece_fold_spec()
+        when the tokenizer lowercases or strips accents), :class:`UnigramSpec` or None."""
+        return self.bpe_spec() or self.wordpiece_fold_spec() or self.unigram_spec()
 
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
         """Token counts of packed UTF-8 documents with the native counter of whichever spec the
-        tokenizer has (host emulation of k_bpe_count / k_wp_count); documents it returns -2 for
+        tokenizer has (host emulation of k_bpe_count / k_wp_count / k_uni_count); documents it returns -2 for
         (added-token text, invalid UTF-8, BPE pre-tokens or SentencePiece-style chunks over 2048 bytes, text that an NFC normalizer
-        may change, WordPiece text with a code point whose place NFD may change under strip_accents) are counted by ``tokenizers``."""
+        may change, WordPiece text with a code point whose place NFD may change under strip_accents, Unigram text
+        with a code point its normalizer changes or the unk piece's own text) are counted by ``tokenizers``."""
         from .. import native
 
         data = np.ascontiguousarray(data, dtype=np.uint8)
         off = np.ascontiguousarray(off, np.int64)
         sp = self.device_spec()
         if sp is None:
-            raise Unexpected("count_native needs a byte-level BPE or a WordPiece tokenizer")
+            raise Unexpected("count_native needs a byte-level BPE, a WordPiece or a Unigram tokenizer")
         out = count_spec(sp, data, off, nthreads).astype(np.int64)
         bad = np.nonzero(out < 0)[0]
         if len(bad):
@@ -525,12 +773,13 @@ class TokenCounterModel:
 
 
 def count_spec(sp, data: np.ndarray, off: np.ndarray, nthreads: int = 8, chunk: int = 0) -> np.ndarray:
-    """The native counter's raw result (int32 counts, -2 = count on the host) for either kind of
+    """The native counter's raw result (int32 counts, -2 = count on the host) for any kind of
     spec; ``chunk`` > 0 counts each chunk-byte range on its own, as the kernels' lanes do."""
     from .. import native
 
     h = native.host()
-    return (h.wp_count if isinstance(sp, WordPieceSpec) else h.bpe_count)(data, off, sp, nthreads, chunk)
+    fn = h.wp_count if isinstance(sp, WordPieceSpec) else (h.uni_count if isinstance(sp, UnigramSpec) else h.bpe_count)
+    return fn(data, off, sp, nthreads, chunk)
 
 
 def train_synthetic_wordpiece(path: str, vocab_size: int = 30522, n_docs: int = 20000, seed: int = 1,
@@ -687,6 +936,97 @@ def train_synthetic_sp_bpe(path: str, vocab_size: int = 32000, layout: str = "L"
         {"type": "Replace", "pattern": {"String": SP_SPACE}, "content": " "}, {"type": "ByteFallback"},
         {"type": "Fuse"}]}
     Tokenizer.from_str(json.dumps(tj))  # the library reads what was written
+    def write(tmp):
+        with open(tmp, "w", encoding="utf-8") as f:
+            json.dump(tj, f, ensure_ascii=False)
+
+    return _save_atomically(path, write)
+
+
+_UNI_SPECIAL = ["<pad>", "</s>", "<unk>"]  # ids 0, 1, 2, as T5 has them
+_uni_trained: dict = {}  # (vocab_size, rule, byte_fallback, n_docs, seed) -> (pieces, charsmap): layouts share a run
+
+
+def _train_unigram_base(vocab_size: int, rule: str, byte_fallback: bool, n_docs: int, seed: int):
+    key = (vocab_size, rule, byte_fallback, n_docs, seed)
+    if key not in _uni_trained:
+        import io
+
+        import sentencepiece as spm
+        from sentencepiece import sentencepiece_model_pb2 as pb
+
+        from ..utils import synth
+
+        texts = synth.make_corpus(n_docs, 1024, seed=seed, vocab="zipf")
+        lines = [ln for t in texts for ln in t.split("\n") if ln.strip()]
+        buf = io.BytesIO()
+        spm.SentencePieceTrainer.train(
+            sentence_iterator=iter(lines), model_writer=buf, vocab_size=vocab_size, model_type="unigram",
+            normalization_rule_name=rule, byte_fallback=byte_fallback, hard_vocab_limit=False, pad_id=0, eos_id=1,
+            unk_id=2, bos_id=-1, pad_piece="<pad>", eos_piece="</s>", unk_piece="<unk>", num_threads=4,
+            max_sentence_length=1 << 20, minloglevel=2)
+        mp = pb.ModelProto()
+        mp.ParseFromString(buf.getvalue())
+        _uni_trained[key] = ([(p.piece, float(p.score)) for p in mp.pieces],
+                             bytes(mp.normalizer_spec.precompiled_charsmap))
+    return _uni_trained[key]
+
+
+def train_synthetic_unigram(path: str, vocab_size: int = 32000, layout: str = "H", rule: str = "nmt_nfkc",
+                            byte_fallback: bool = False, prepend_scheme: str = "always", n_docs: int = 20000,
+                            seed: int = 1) -> str:
+    """Train a Unigram tokenizer with ``sentencepiece`` on the synthetic Zipf corpus and save it as
+    ``path`` (kept if it already exists), written as the T5 / mT5 / XLM-R files are: ``<pad>``,
+    ``</s>``, ``<unk>`` in front of the vocabulary and registered as added tokens, a template that
+    puts ``</s>`` behind the text, the trained model's ``precompiled_charsmap`` of normalisation
+    rule ``rule`` (``nmt_nfkc``, ``nfkc``; ``identity`` has none) in a Precompiled normalizer, and
+
+    * ``layout="H"`` (the hub files): normalizer Sequence[Precompiled, Replace(Regex " {2,}" -> " ")],
+      pre-tokenizer Sequence[WhitespaceSplit, Metaspace("▁", always)];
+    * ``layout="C"`` (transformers' SpmConverter): normalizer Sequence[Precompiled, Strip(right),
+      Replace(Regex " {2,}" -> "▁")], pre-tokenizer Metaspace("▁", ``prepend_scheme``, split).
+
+    The stand-in for the files of those models, which cannot be downloaded here; the counts differ
+    from theirs, the work per byte is of the same kind."""
+    if os.path.isfile(path):
+        return path
+    if layout not in ("H", "C") or rule not in ("nmt_nfkc", "nfkc", "identity") or prepend_scheme not in ("always", "first"):
+        raise ValueError("train_synthetic_unigram: layout is H or C, rule nmt_nfkc, nfkc or identity, "
+                         "prepend_scheme always or first")
+    import base64
+
+    from tokenizers import Tokenizer
+
+    pieces, charsmap = _train_unigram_base(vocab_size, rule, byte_fallback, n_docs, seed)
+    ids = {p: i for i, (p, _) in enumerate(pieces)}
+    seq = [{"type": "Precompiled", "precompiled_charsmap": base64.b64encode(charsmap).decode("ascii")}] if charsmap else []
+    meta = {"type": "Metaspace", "replacement": SP_SPACE, "prepend_scheme": prepend_scheme if layout == "C" else "always",
+            "split": True}
+    if layout == "H":
+        seq.append({"type": "Replace", "pattern": {"Regex": " {2,}"}, "content": " "})
+        pre = {"type": "Sequence", "pretokenizers": [{"type": "WhitespaceSplit"}, meta]}
+    else:
+        seq += [{"type": "Strip", "strip_left": False, "strip_right": True},
+                {"type": "Replace", "pattern": {"Regex": " {2,}"}, "content": SP_SPACE}]
+        pre = meta
+    eos = ids["</s>"]
+    tj = {
+        "version": "1.0", "truncation": None, "padding": None,
+        "added_tokens": [{"id": ids[t], "content": t, "single_word": False, "lstrip": False, "rstrip": False,
+                          "normalized": False, "special": True} for t in _UNI_SPECIAL],
+        "normalizer": {"type": "Sequence", "normalizers": seq},
+        "pre_tokenizer": pre,
+        "post_processor": {
+            "type": "TemplateProcessing",
+            "single": [{"Sequence": {"id": "A", "type_id": 0}}, {"SpecialToken": {"id": "</s>", "type_id": 0}}],
+            "pair": [{"Sequence": {"id": "A", "type_id": 0}}, {"SpecialToken": {"id": "</s>", "type_id": 0}},
+                     {"Sequence": {"id": "B", "type_id": 0}}, {"SpecialToken": {"id": "</s>", "type_id": 0}}],
+            "special_tokens": {"</s>": {"id": "</s>", "ids": [eos], "tokens": ["</s>"]}}},
+        "decoder": dict(meta),
+        "model": {"type": "Unigram", "unk_id": ids["<unk>"], "vocab": [[p, s] for p, s in pieces],
+                  "byte_fallback": byte_fallback}}
+    Tokenizer.from_str(json.dumps(tj))  # the library reads what was written
+
     def write(tmp):
         with open(tmp, "w", encoding="utf-8") as f:
             json.dump(tj, f, ensure_ascii=False)

@@ -131,6 +131,8 @@ _SIGS = {
     "tb_bpe_count": [_P, _P, _P, _P, _P, _I32, _P],
     "tb_wp_count": [_P, _P, _P, _P, _P, _I32, _P],
     "tb_sizeof_wp": [],
+    "tb_uni_count": [_P, _P, _P, _P, _P, _I32, _P],
+    "tb_sizeof_uni": [],
     "tb_abi_version": [], "tb_block_threads": [], "tb_phase_slots": [], "tb_stage_waves": [],
     "tb_sizeof_pre_doc": [], "tb_sizeof_gr_export": [], "tb_sizeof_gate": [], "tb_sizeof_resolve": [],
     "tb_sizeof_bpe": [], "tb_sizeof_plan": [], "tb_sizeof_stage": [], "tb_sizeof_c4": [],
@@ -193,6 +195,16 @@ class WpTables(_TokTables):
 
     def __init__(self, h, spec, static):
         super().__init__(h.wp_params, spec, {"slots": spec.slots, "pool": spec.pool, "added": spec.added, **static})
+
+
+class UniTables(_TokTables):
+    """csrc/common/unigram.h DevUni of a models/tokenizer.py UnigramSpec: the spec carries every
+    table, the class table of its own normalizer included."""
+
+    def __init__(self, h, spec):
+        super().__init__(h.uni_params, spec, {
+            "slots": spec.slots, "pool": spec.pool, "added": spec.added, "cls1": spec.cls1, "cls2": spec.cls2,
+            "aoff": np.array(spec.added_off or [0], dtype=np.int32)})
 
 
 def declare(lib: ctypes.CDLL) -> None:
@@ -476,15 +488,31 @@ class Kernels:
                                   _ptr(n_dev), n_max, counts.data_ptr())
         _check(rc, "tb_wp_count")
 
-    def token_tables(self, spec):
-        """The device tables of a token counter spec of either kind."""
-        from ..models.tokenizer import WordPieceSpec
+    def uni_tables(self, spec) -> UniTables:
+        from .. import native
 
+        return UniTables(native.host(), spec)
+
+    def uni_count(self, tabs: UniTables, text, off, n_dev, n_max: int, counts):
+        """k_uni_count: Unigram token counts under bpe_count's contract (csrc/hip/unigram.hip)."""
+        if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
+            raise DeviceError("uni_count: operand shapes")
+        rc = self.lib.tb_uni_count(self.stream(), tabs.block, text.data_ptr(), off.data_ptr(),
+                                   _ptr(n_dev), n_max, counts.data_ptr())
+        _check(rc, "tb_uni_count")
+
+    def token_tables(self, spec):
+        """The device tables of a token counter spec of any kind."""
+        from ..models.tokenizer import UnigramSpec, WordPieceSpec
+
+        if isinstance(spec, UnigramSpec):
+            return self.uni_tables(spec)
         return self.wp_tables(spec) if isinstance(spec, WordPieceSpec) else self.bpe_tables(spec)
 
     def token_count(self, tabs, text, off, n_dev, n_max: int, counts):
-        """k_wp_count, k_bpe_count or k_bpe_split_count, by the kind of ``tabs``."""
-        fn = self.wp_count if isinstance(tabs, WpTables) else self.bpe_count
+        """k_wp_count, k_uni_count, k_bpe_count or k_bpe_split_count, by the kind of ``tabs``."""
+        fn = self.wp_count if isinstance(tabs, WpTables) else (
+            self.uni_count if isinstance(tabs, UniTables) else self.bpe_count)
         fn(tabs, text, off, n_dev, n_max, counts)
 
     def resolve(self, rp, recs, ndocs, flags, versions, fail, status, fver, lanes, sc, out, out_off, rows, err):

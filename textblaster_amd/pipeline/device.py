@@ -581,9 +581,9 @@ class DeviceRunner:
                     self.resolve_t = self._to_dev(blob)
                     # int64 fields per document read from each record buffer (launch-time check)
                     self.resolve_need = [w for w, _ in self.stage_layout] + [7] * len(plan.c4_steps)
-            # trailing TokenCounter steps with a byte-level BPE (GPT-2 or split-regex) or a WordPiece
-            # tokenizer: counted on the device after K16 (token_counters: [(step, BpeSpec | WordPieceSpec)];
-            # device_tokens=0 leaves them to the host)
+            # trailing TokenCounter steps with a byte-level BPE (GPT-2 or split-regex), a WordPiece or a
+            # Unigram tokenizer: counted on the device after K16 (token_counters: [(step, BpeSpec |
+            # WordPieceSpec | UnigramSpec)]; device_tokens=0 leaves them to the host)
             self.bpe = []
             if self.resolve_t is not None and tu.device_tokens:
                 self.bpe = [(i, self.k.token_tables(sp)) for i, sp in (token_counters or [])]
@@ -1409,8 +1409,8 @@ class EmulatedRunner:
                                                           [np.ascontiguousarray(o) for _, o in vl])
             resolved = Resolved(fail, st, out, out_off, rows)
             if self.bpe:
-                # k_bpe_count's / k_bpe_split_count's / k_wp_count's algorithm (csrc/common/bpe.h,
-                # bpe_split.h, wordpiece.h) over the kept outputs
+                # k_bpe_count's / k_bpe_split_count's / k_wp_count's / k_uni_count's algorithm
+                # (csrc/common/bpe.h, bpe_split.h, wordpiece.h, unigram.h) over the kept outputs
                 from ..models.tokenizer import count_spec
 
                 nk = int(np.count_nonzero(st == 0))

@@ -176,7 +176,8 @@ class Engine:
         # ByteLevel regex, or the Llama-3 / cl100k_base / Qwen2 Split patterns), a SentencePiece-style
         # character-level BPE (Llama-2 / Mistral / Gemma) or a BERT-style WordPiece are counted by the
         # device path on the kept outputs (k_bpe_count / k_bpe_split_count / k_bpe_sp_count /
-        # k_wp_count); the others on the host
+        # k_wp_count), and so are Unigram files in the layouts of T5 / mT5 / XLM-R (k_uni_count); the
+        # others on the host
         from .device import trailing_token_counters
 
         self._trailing_tc = set(trailing_token_counters(self.plan))
@@ -677,7 +678,7 @@ class Engine:
             rec = np.full(ndocs, -1, dtype=np.int64)
             if len(alive) and resolved is not None and resolved.n_kept_final() == len(alive):
                 # K16 agreed: final kept output k is alive[k]; its count came from k_bpe_count /
-                # k_bpe_split_count / k_wp_count / k_wp_count_fold (or -2: added-token text, a BPE
+                # k_bpe_split_count / k_wp_count / k_wp_count_fold / k_uni_count (or -2: added-token text, a BPE
                 # pre-token over 2048 bytes, accent-stripped WordPiece text with a code point NFD may
                 # reorder -> the tokenizer, like unsupported tokenizers)
                 dev = resolved.kept_tokens(i)

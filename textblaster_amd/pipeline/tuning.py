@@ -48,7 +48,7 @@ class DeviceTuning:
     gate: bool = True              # step gating: later passes skip documents an earlier pass filtered
     lid_gate: bool = True          # a language-id pass gates the stage kernels after it
     device_resolve: bool = True    # K16: records resolved and outputs compacted on the device
-    # trailing TokenCounter steps counted on the device (k_bpe_count, k_bpe_split_count, k_wp_count)
+    # trailing TokenCounter steps counted on the device (k_bpe_count, k_bpe_split_count, k_wp_count, k_uni_count)
     device_tokens: bool = True
     device_meta: bool = True       # K18: the output metadata column formatted on the device (profiles/device_meta/)
     dict_marks: bool = True        # dictionary-script docs: host ICU word marks, stay on the device

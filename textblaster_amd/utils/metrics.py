@@ -88,11 +88,12 @@ DEVICE_META_FALLBACK_TOTAL = Counter("tb_device_meta_fallback_total",
 BPE_HOST_DOCS_TOTAL = Counter("tb_bpe_host_docs_total",
                               "Kept documents whose TokenCounter count the device handed to the host tokenizer "
                               "(added-token text, invalid UTF-8, a BPE pre-token over 2048 bytes, accent-stripped "
-                              "WordPiece text with a code point NFD may reorder, or a tokenizer with no device "
-                              "counter).", registry=REGISTRY)
+                              "WordPiece text with a code point NFD may reorder, Unigram text with a code point its "
+                              "normalizer drops, replaces or joins to a neighbour or with the unk piece's text, or a "
+                              "tokenizer with no device counter).", registry=REGISTRY)
 BPE_DEVICE_DOCS_TOTAL = Counter("tb_bpe_device_docs_total",
                                 "Kept documents whose TokenCounter count came from a device kernel (k_bpe_count, "
-                                "k_bpe_split_count, k_wp_count, k_wp_count_fold).",
+                                "k_bpe_split_count, k_wp_count, k_wp_count_fold, k_uni_count).",
                                 registry=REGISTRY)
 RANK = Gauge("tb_rank", "Data-parallel rank of this process.", registry=REGISTRY)
 WORLD_SIZE = Gauge("tb_world_size", "Number of data-parallel ranks.", registry=REGISTRY)
