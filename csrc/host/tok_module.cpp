@@ -53,7 +53,9 @@ struct WpSpecArrays {
 struct UniSpecArrays {
   Arr<uint64_t> slots;
   Arr<uint8_t> pool, added, cls2, sp;
-  Arr<uint16_t> cls1;
+  Arr<uint16_t> cls1, map1, map2;
+  Arr<uint32_t> map_rec;
+  Arr<uint8_t> map_pool;
   std::vector<int32_t> added_off;
 };
 
@@ -73,6 +75,10 @@ UniSpecView uni_view(const py::object& s, UniSpecArrays& a) {
   v.longest = s.attr("longest").cast<int32_t>();
   v.post_add = s.attr("post_add").cast<int32_t>();
   v.unk_score = s.attr("unk_score").cast<double>();
+  v.map1 = spec_array(s, "map1", a.map1);
+  v.map2 = spec_array(s, "map2", a.map2);
+  v.map_rec = spec_array(s, "map_rec", a.map_rec);
+  v.map_pool = spec_array(s, "map_pool", a.map_pool);
   return v;
 }
 
@@ -188,12 +194,15 @@ void register_tok(py::module_& m) {
     TB_OFF(u, DevUni, asc2); TB_OFF(u, DevUni, asc3); TB_OFF(u, DevUni, amask); TB_OFF(u, DevUni, unk_score);
     TB_OFF(u, DevUni, mask); TB_OFF(u, DevUni, flags); TB_OFF(u, DevUni, sp_bytes); TB_OFF(u, DevUni, sp_len);
     TB_OFF(u, DevUni, longest_cp); TB_OFF(u, DevUni, longest); TB_OFF(u, DevUni, post_add); TB_OFF(u, DevUni, n_added);
+    TB_OFF(u, DevUni, map1); TB_OFF(u, DevUni, map2); TB_OFF(u, DevUni, mrec); TB_OFF(u, DevUni, mpool);
 #undef TB_OFF
     m.attr("DEV_UNI_OFFSETS") = u;
     m.attr("SIZEOF_DEV_UNI") = sizeof(DevUni);
     uc["UNI_KEEP"] = (int)UNI_KEEP; uc["UNI_SPACE"] = (int)UNI_SPACE; uc["UNI_HOST"] = (int)UNI_HOST;
     uc["UNI_BYTE_FALLBACK"] = kUniByteFallback; uc["UNI_MAX_PIECE_CP"] = kUniMaxPieceCp;
     uc["UNI_MAX_PIECE_BYTES"] = kUniMaxPieceBytes;
+    uc["UNI_MAP"] = (int)UNI_MAP; uc["UNI_MAX_MAP_BYTES"] = kUniMaxMapBytes; uc["UNI_MAP_NONE"] = (int)kUniMapNone;
+    uc["UNI_REC_LEN"] = kUniRecLen; uc["UNI_REC_JOIN"] = kUniRecJoin;
     m.attr("UNI_CONSTANTS") = uc;
   }
   // ---- byte-level BPE token counting (csrc/common/bpe.h; device kernel csrc/hip/bpe.hip) ----
@@ -450,12 +459,13 @@ void register_tok(py::module_& m) {
     return py::make_tuple(to_numpy(std::move(slots)), (uint32_t)(cap - 1));
   });
   m.def("uni_count", [](Arr<uint8_t> data, Arr<int64_t> off, py::object spec, int nthreads, int64_t chunk) {
-    // host emulation of k_uni_count: per document the token count, or kBpeHost. chunk > 0: the wave
-    // split - the words starting in each chunk-byte range counted independently (uni_count_range),
-    // as the kernel's lanes do
+    // host emulation of k_uni_count, and of k_uni_count_map for a spec with a map: per document the
+    // token count, or kBpeHost. chunk > 0: the wave split - the words starting in each chunk-byte
+    // range counted independently (uni_count_range / unim_count_range), as the kernel's lanes do
     UniSpecArrays arrays;
     const UniSpecView view = uni_view(spec, arrays);
     const DevUni T = uni_fill_params(view, uni_host_ptrs(view));
+    const bool map = uni_has_map(T);
     const int64_t nd = off.size() - 1;
     std::vector<int32_t> out(nd > 0 ? nd : 0);
     const uint8_t* d = data.data();
@@ -473,13 +483,14 @@ void register_tok(py::module_& m) {
             const uint8_t* b = d + o[k];
             const int64_t n = o[k + 1] - o[k];
             if (chunk <= 0) {
-              out[k] = uni_count_doc(T, b, n, R);
+              out[k] = map ? unim_count_doc(T, b, n, R) : uni_count_doc(T, b, n, R);
               continue;
             }
             int64_t tot = T.post_add;
             bool bad = T.n_added && uni_has_added(T, b, n, 0, n);
             for (int64_t s0 = 0; s0 < n && !bad; s0 += chunk) {
-              const int64_t x = uni_count_range(T, b, n, s0, std::min(n, s0 + chunk), R);
+              const int64_t s1 = std::min(n, s0 + chunk);
+              const int64_t x = map ? unim_count_range(T, b, n, s0, s1, R) : uni_count_range(T, b, n, s0, s1, R);
               if (x < 0) bad = true;
               tot += x;
             }
@@ -497,7 +508,9 @@ void register_tok(py::module_& m) {
     UniPtrs p;
     addr(ptrs, "slots", p.slots); addr(ptrs, "pool", p.pool); addr(ptrs, "added", p.added);
     addr(ptrs, "cls1", p.cls1); addr(ptrs, "cls2", p.cls2); addr(ptrs, "aoff", p.aoff);
+    addr(ptrs, "map1", p.map1); addr(ptrs, "map2", p.map2); addr(ptrs, "map_rec", p.map_rec);
+    addr(ptrs, "map_pool", p.map_pool);
     const DevUni T = uni_fill_params(view, p);
-    return block_bytes(T, offsetof(DevUni, n_added) + sizeof T.n_added);
+    return block_bytes(T, offsetof(DevUni, mpool) + sizeof T.mpool);
   }, py::arg("spec"), py::arg("ptrs"));
 }

@@ -67,6 +67,11 @@ struct UniSpecView {
   uint32_t mask = 0, flags = 0;
   int32_t longest_cp = 0, longest = 0, post_add = 0;
   double unk_score = 0;
+  // the normalizer's replacements; all empty: a spec without a map
+  TokSpan<uint16_t> map1, map2;
+  TokSpan<uint32_t> map_rec;
+  TokSpan<uint8_t> map_pool;
+  bool mapped() const { return map1.n || map2.n || map_rec.n || map_pool.n; }
 };
 
 // ---- where the arrays a block points to are: in host memory, or in HBM ----
@@ -101,6 +106,9 @@ struct UniPtrs {
   const uint8_t *pool = nullptr, *added = nullptr, *cls2 = nullptr;
   const uint16_t* cls1 = nullptr;
   const int32_t* aoff = nullptr;
+  const uint16_t *map1 = nullptr, *map2 = nullptr;  // a spec with a map
+  const uint32_t* map_rec = nullptr;
+  const uint8_t* map_pool = nullptr;
 };
 
 // the static tables in host memory
@@ -151,6 +159,10 @@ inline UniPtrs uni_host_ptrs(const UniSpecView& v) {
   p.cls1 = v.cls1.p;
   p.cls2 = v.cls2.p;
   p.aoff = v.added_off.p;
+  p.map1 = v.map1.p;
+  p.map2 = v.map2.p;
+  p.map_rec = v.map_rec.p;
+  p.map_pool = v.map_pool.p;
   return p;
 }
 
@@ -231,6 +243,25 @@ inline const char* uni_spec_error(const UniSpecView& v) {
   if (v.sp.n < 1 || v.sp.n > 4) return "unigram: the replacement character has 1 to 4 bytes";
   if (v.flags & ~kUniByteFallback) return "unigram: flags";
   if (!std::isfinite(v.unk_score)) return "unigram: unk_score";
+  if (!v.mapped()) return nullptr;
+  if (v.map1.n != kUniClsStage1) return "unigram: map1 needs one entry per 128 code points";
+  if (v.map_rec.n == 0 || v.map_pool.n == 0) return "unigram: a map needs records and a pool";
+  for (size_t i = 0; i < v.map1.n; ++i)
+    if (((size_t)v.map1.p[i] + 1) * 128 > v.map2.n) return "unigram: a map block lies past map2";
+  for (size_t i = 0; i < v.map2.n; ++i)
+    if (v.map2.p[i] != kUniMapNone && v.map2.p[i] >= v.map_rec.n) return "unigram: map2 names a record past map_rec";
+  for (size_t i = 0; i < v.map_rec.n; ++i) {
+    const size_t nb = v.map_rec.p[i] & kUniRecLen;
+    if (nb > (size_t)kUniMaxMapBytes) return "unigram: a replacement exceeds the cap";
+    if ((size_t)(v.map_rec.p[i] >> 8) + nb > v.map_pool.n) return "unigram: a replacement lies past map_pool";
+  }
+  for (uint32_t c = 0; c < 0x110000; ++c) {  // the counter looks every map code point's record up
+    const int k = (v.cls2.p[(size_t)v.cls1.p[c >> 7] * 32 + ((c & 127) >> 2)] >> (2 * (c & 3))) & 3;
+    const uint16_t r = v.map2.p[(size_t)v.map1.p[c >> 7] * 128 + (c & 127)];
+    if (k == UNI_MAP && (r == kUniMapNone || (v.map_rec.p[r] & kUniRecJoin))) return "unigram: a map code point has no record";
+    if (k != UNI_MAP && r != kUniMapNone && !(k == UNI_SPACE && (v.map_rec.p[r] & kUniRecJoin)))
+      return "unigram: a record of a code point that is not of the map class";
+  }
   return nullptr;
 }
 
@@ -326,6 +357,14 @@ inline DevUni uni_fill_params(const UniSpecView& v, const UniPtrs& p) {
   T.longest_cp = v.longest_cp;
   T.longest = v.longest;
   T.post_add = v.post_add;
+  if (v.mapped()) {
+    T.map1 = p.map1;
+    T.map2 = p.map2;
+    T.mrec = p.map_rec;
+    T.mpool = p.map_pool;
+    if (!uni_has_map(T) || T.map2 == nullptr || T.mrec == nullptr || T.mpool == nullptr)
+      throw std::invalid_argument("unigram: a table of the map has no address");
+  }
   if (!uni_params_ok(T)) throw std::invalid_argument("unigram: a table the counter reads has no address");
   return T;
 }

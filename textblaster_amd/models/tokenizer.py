@@ -31,7 +31,9 @@ Unigram files (T5, mT5, XLM-R: a Precompiled normalizer, white-space splitting a
 of two layouts) get a :class:`UnigramSpec` (:meth:`TokenCounterModel.unigram_spec`; csrc/common/unigram.h,
 k_uni_count): the pieces with their scores in a hash table over a byte pool, and a class table probed
 from the file's own normalizer that says which code points it keeps, turns into a space, or changes
-(documents with one of those are counted by ``tokenizers``).
+(documents with one of those are counted by ``tokenizers``). The mapped spec
+(:meth:`TokenCounterModel.unigram_map_spec`, k_uni_count_map, ``TB_TUNE=uni_map=1``) also carries what
+the normalizer changes those code points into, for the counter to apply itself.
 
 A spec is data only. The host module reads it as it stands (``bpe_count`` / ``wp_count`` for the host
 emulation (``uni_count`` for Unigram), ``bpe_params`` / ``wp_params`` / ``uni_params`` for the kernels' parameter block), and one validator and
@@ -479,12 +481,24 @@ class UnigramSpec:
     added_off: List[int]   # [n_added + 1]
     post_add: int          # tokens the post-processor adds
     layout: str = "H"      # "H" (hub files) or "C" (converted files): see build_unigram_spec
+    # the replacements of the normalizer (build_unigram_spec(mapped=True)); empty: a spec without a map
+    map1: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint16))     # uint16 [0x110000 >> 7]: block of map2
+    map2: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint16))     # uint16, 128 per block: record or UNI_MAP_NONE
+    map_rec: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint32))  # uint32: offset in map_pool << 8 | UNI_REC_JOIN | bytes
+    map_pool: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint8))  # uint8: the outputs, white space as 0x20
+
+    @property
+    def mapped(self) -> bool:
+        return len(self.map1) > 0
 
 
 # csrc/common/unigram.h (pinned to the header's values by tests/test_unigram.py through UNI_CONSTANTS)
-UNI_KEEP, UNI_SPACE, UNI_HOST = 0, 1, 2
+UNI_KEEP, UNI_SPACE, UNI_HOST, UNI_MAP = 0, 1, 2, 3
 UNI_BYTE_FALLBACK = 1
 UNI_MAX_PIECE_CP, UNI_MAX_PIECE_BYTES = 32, 128
+UNI_MAX_MAP_BYTES = 32   # a replacement with more bytes leaves its code point to the host (nmt_nfkc: U+FDFA, 33)
+UNI_MAP_NONE = 0xFFFF    # map2: the code point has no record
+UNI_REC_LEN, UNI_REC_JOIN = 0x7F, 0x80  # map_rec: the length's bits; a space code point that joins the grapheme before it
 # Rust's char::is_whitespace (White_Space): what WhitespaceSplit separates on and Strip removes
 RUST_WHITESPACE = frozenset([*range(9, 14), 0x20, 0x85, 0xA0, 0x1680, *range(0x2000, 0x200B), 0x2028, 0x2029, 0x202F,
                              0x205F, 0x3000])
@@ -561,10 +575,6 @@ def unigram_classes(charsmap: Optional[str], layout: str) -> np.ndarray:
     share a grapheme with a neighbour (Grapheme_Cluster_Break Extend, ZWJ, SpacingMark, Prepend, L,
     V, T; the combining marks and unassigned code points of Python's own Unicode data): Precompiled looks a whole grapheme
     under 6 bytes up and replaces all of it by the shortest matching prefix's output."""
-    import unicodedata
-
-    from .. import native
-
     out = unigram_probe(charsmap)
     cls = np.full(0x110000, UNI_HOST, dtype=np.uint8)
     for c, o in enumerate(out):
@@ -576,23 +586,128 @@ def unigram_classes(charsmap: Optional[str], layout: str) -> np.ndarray:
             else:
                 cls[c] = UNI_KEEP
     if charsmap is not None:
-        # the library's segmentation may know a newer Unicode than any one source here: the union of
-        # ICU's property, Python's combining marks and unassigned code points, and the regex
-        # module's property where it is installed
-        joiner = native.host().uni_grapheme_joiners().astype(bool)
-        for c in range(0x80, 0x110000):
-            if unicodedata.category(chr(c)) in ("Mn", "Me", "Mc", "Cn"):
-                joiner[c] = True
-        try:
-            import regex
-        except ImportError:
-            regex = None
-        if regex is not None:
-            text = "".join(chr(c) for c in range(0x110000) if not 0xD800 <= c < 0xE000)
-            for hit in regex.finditer(_UNI_JOINERS, text):
-                joiner[ord(hit.group())] = True
-        cls[joiner & (cls == UNI_KEEP)] = UNI_HOST
+        cls[_unigram_joiners() & (cls == UNI_KEEP)] = UNI_HOST
     return cls
+
+
+def _unigram_joiners() -> np.ndarray:
+    """bool [0x110000]: the code points that can share a grapheme with a neighbour. The library's
+    segmentation may know a newer Unicode than any one source here: the union of ICU's property,
+    Python's combining marks and unassigned code points, and the regex module's property where it
+    is installed."""
+    import unicodedata
+
+    from .. import native
+
+    joiner = native.host().uni_grapheme_joiners().astype(bool)
+    for c in range(0x80, 0x110000):
+        if unicodedata.category(chr(c)) in ("Mn", "Me", "Mc", "Cn"):
+            joiner[c] = True
+    try:
+        import regex
+    except ImportError:
+        regex = None
+    if regex is not None:
+        text = "".join(chr(c) for c in range(0x110000) if not 0xD800 <= c < 0xE000)
+        for hit in regex.finditer(_UNI_JOINERS, text):
+            joiner[ord(hit.group())] = True
+    return joiner
+
+
+def unigram_map(charsmap: Optional[str], layout: str):
+    """(cls, outputs, joins): :func:`unigram_classes` with UNI_MAP for the host code points whose
+    replacement the device counter applies itself, code point -> the replacement's bytes as the
+    counter reads them (white space as 0x20; empty: the code point is dropped), and the space code
+    points that are grapheme joiners (U+200C behind nmt_nfkc). Precompiled looks a whole grapheme
+    under 6 bytes up and replaces all of it by its first code point's output, so a map code point
+    swallows such a joiner: the counter hands a document with that pair to the host.
+
+    A host code point becomes UNI_MAP when it is no surrogate and no grapheme joiner, its output on
+    its own differs from it, has at most UNI_MAX_MAP_BYTES bytes and no U+2581, every white-space
+    code point of the output separates words in the layout (H: any, C: U+0020 only, as for kept
+    white space), and between two letters the normalizer gives the same output: the code point is a
+    grapheme of its own. The output's code points are not classified again: the library neither
+    segments nor normalises them a second time, so they are word text, or 0x20."""
+    cls = unigram_classes(charsmap, layout)
+    outputs = {}
+    if charsmap is None:
+        return cls, outputs, []
+    import base64
+
+    from tokenizers import normalizers
+
+    f = normalizers.Precompiled(base64.b64decode(charsmap)).normalize_str
+    joiner = _unigram_joiners()
+    for c in np.nonzero((cls == UNI_HOST) & ~joiner)[0].tolist():
+        if 0xD800 <= c < 0xE000:
+            continue
+        o = f(chr(c))
+        if o == chr(c) or SP_SPACE in o or len(o.encode("utf-8")) > UNI_MAX_MAP_BYTES:
+            continue
+        white = [x for x in o if ord(x) in RUST_WHITESPACE]
+        if layout != "H" and any(x != " " for x in white):
+            continue
+        if f("a" + chr(c) + "b") != "a" + o + "b":
+            continue
+        cls[c] = UNI_MAP
+        outputs[c] = "".join(" " if ord(x) in RUST_WHITESPACE else x for x in o).encode("utf-8")
+    return cls, outputs, np.nonzero((cls == UNI_SPACE) & joiner)[0].tolist()
+
+
+def _two_stage_map(outputs: dict, joins=()):
+    """code point -> bytes as UnigramSpec's map1, map2, map_rec, map_pool; equal outputs share a
+    record, and the code points of ``joins`` one that is UNI_REC_JOIN. Both of the last two hold
+    one entry at least, so that every table has an address."""
+    recs, pool, index = [], bytearray(), np.full(0x110000, UNI_MAP_NONE, dtype=np.uint16)
+    seen = {}
+    if len(joins):
+        recs.append(UNI_REC_JOIN)
+        index[np.asarray(joins, dtype=np.int64)] = 0
+    for c in sorted(outputs):
+        o = outputs[c]
+        if o not in seen:
+            if len(recs) >= UNI_MAP_NONE:
+                raise ValueError("unigram map: more replacements than map2 can name")
+            seen[o] = len(recs)
+            recs.append((len(pool) << 8) | len(o))
+            pool += o
+        index[c] = seen[o]
+    blocks, inverse = np.unique(index.reshape(-1, 128), axis=0, return_inverse=True)
+    # block 0 of np.unique is not the empty one in general; any order serves the lookup
+    return (inverse.reshape(-1).astype(np.uint16), np.ascontiguousarray(blocks.reshape(-1)),
+            np.array(recs or [0], dtype=np.uint32), np.frombuffer(bytes(pool) or b"\0", dtype=np.uint8).copy())
+
+
+def _unigram_map_table(charsmap: Optional[str], layout: str, cache_dir: Optional[str]):
+    """(cls1, cls2, map1, map2, map_rec, map_pool) of a mapped spec, from the cache file next to
+    the tokenizer when there is one (a file of its own: unigram_classes.*.npz stays as it is)."""
+    import hashlib
+
+    names = ("cls1", "cls2", "map1", "map2", "map_rec", "map_pool")
+    kinds = (np.uint16, np.uint8, np.uint16, np.uint16, np.uint32, np.uint8)
+    key = hashlib.sha256(f"m2:{UNI_MAX_MAP_BYTES}:{layout}:{charsmap or ''}".encode("utf-8")).hexdigest()[:16]
+    path = os.path.join(cache_dir, f"unigram_map.{key}.npz") if cache_dir else None
+    if path and os.path.isfile(path):
+        try:
+            with np.load(path) as z:
+                t = tuple(z[n].astype(k) for n, k in zip(names, kinds))
+            if (t[0].shape == t[2].shape == (0x110000 >> 7,) and (int(t[0].max()) + 1) * 32 <= len(t[1])
+                    and (int(t[2].max()) + 1) * 128 <= len(t[3]) and len(t[4]) and len(t[5])):
+                return t  # the parameter block's validator checks the records
+        except (OSError, ValueError, KeyError):
+            pass
+    cls, outputs, joins = unigram_map(charsmap, layout)
+    t = _two_stage_2bit(cls) + _two_stage_map(outputs, joins)
+    if path:
+        def write(tmp):
+            with open(tmp, "wb") as f:
+                np.savez_compressed(f, **dict(zip(names, t)))
+
+        try:
+            _save_atomically(path, write)
+        except OSError:
+            pass  # a read-only tokenizer directory: probed again next time
+    return t
 
 
 def _unigram_class_table(charsmap: Optional[str], layout: str, cache_dir: Optional[str]):
@@ -622,7 +737,7 @@ def _unigram_class_table(charsmap: Optional[str], layout: str, cache_dir: Option
     return c1, c2
 
 
-def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None) -> Optional[UnigramSpec]:
+def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None, mapped: bool = False) -> Optional[UnigramSpec]:
     """UnigramSpec of a parsed tokenizer.json, or None when the tokenizer is not a Unigram model the
     device counter reproduces exactly: ``unk_id`` set, no duplicate pieces, finite scores, with
     ``byte_fallback`` all 256 ``<0xNN>`` pieces, no truncation / padding, a known post-processor, at
@@ -637,7 +752,11 @@ def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None) -> Optional[Un
 
     In both the count of a document is the sum over its words, each encoded as "▁" + word. The
     class table comes from probing the file's own Precompiled normalizer (:func:`unigram_classes`)
-    and is cached in ``cache_dir``."""
+    and is cached in ``cache_dir``.
+
+    ``mapped``: the spec also carries the normalizer's replacements (:func:`unigram_map`; class
+    UNI_MAP in the table, ``map1`` / ``map2`` / ``map_rec`` / ``map_pool``), and the counter applies
+    them instead of handing the document to the host (k_uni_count_map)."""
     import math
 
     from .. import native
@@ -681,8 +800,12 @@ def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None) -> Optional[Un
     if len(contents) > SPLIT_MAX_ADDED or len(added) > SPLIT_MAX_ADDED_BYTES:
         return None
     layout, charsmap = lay
+    maps = ()
     try:
-        cls1, cls2 = _unigram_class_table(charsmap, layout, cache_dir)
+        if mapped:
+            cls1, cls2, *maps = _unigram_map_table(charsmap, layout, cache_dir)
+        else:
+            cls1, cls2 = _unigram_class_table(charsmap, layout, cache_dir)
     except Exception:  # noqa: BLE001 - a charsmap the library does not read
         return None
     off = np.zeros(len(pieces) + 1, dtype=np.int64)
@@ -692,7 +815,7 @@ def build_unigram_spec(tj: dict, cache_dir: Optional[str] = None) -> Optional[Un
     assert math.isfinite(unk_score)
     return UnigramSpec(slots, int(mask), pool, cls1, cls2, np.frombuffer(SP_SPACE.encode("utf-8"), dtype=np.uint8).copy(),
                        UNI_BYTE_FALLBACK if byte_fallback else 0, unk_score, longest_cp, longest, added, aoff, post,
-                       layout)
+                       layout, *maps)
 
 
 class TokenCounterModel:
@@ -705,6 +828,7 @@ class TokenCounterModel:
         self._wp_spec = False
         self._wp_fold_spec = False
         self._uni_spec = False
+        self._uni_map_spec = False
 
     def count(self, texts: List[str]) -> List[int]:
         if not texts:
@@ -747,10 +871,24 @@ class TokenCounterModel:
                 self._uni_spec = build_unigram_spec(json.load(f), os.path.dirname(os.path.abspath(self.path)))
         return self._uni_spec
 
-    def device_spec(self):
+    def unigram_map_spec(self) -> Optional[UnigramSpec]:
+        """:meth:`unigram_spec` with the normalizer's replacements for the counter to apply
+        (``build_unigram_spec(mapped=True)``); built once, its tables cached next to the tokenizer
+        file."""
+        if self._uni_map_spec is False:
+            with open(self.path, encoding="utf-8") as f:
+                self._uni_map_spec = build_unigram_spec(json.load(f), os.path.dirname(os.path.abspath(self.path)),
+                                                        mapped=True)
+        return self._uni_map_spec
+
+    def device_spec(self, uni_map: bool = False):
         """The spec the device path counts with: :class:`BpeSpec`, :class:`WordPieceSpec` (folding
-        when the tokenizer lowercases or strips accents), :class:`UnigramSpec` or None."""
-        return self.bpe_spec() or self.wordpiece_fold_spec() or self.unigram_spec()
+        when the tokenizer lowercases or strips accents), :class:`UnigramSpec` (``uni_map``: the one
+        with the normalizer's replacements, DeviceTuning.uni_map) or None."""
+        sp = self.bpe_spec() or self.wordpiece_fold_spec()
+        if sp is None and uni_map:
+            return self.unigram_map_spec()
+        return sp or self.unigram_spec()
 
     def count_native(self, data: np.ndarray, off: np.ndarray, nthreads: int = 8) -> np.ndarray:
         """Token counts of packed UTF-8 documents with the native counter of whichever spec the

@@ -199,12 +199,14 @@ class WpTables(_TokTables):
 
 class UniTables(_TokTables):
     """csrc/common/unigram.h DevUni of a models/tokenizer.py UnigramSpec: the spec carries every
-    table, the class table of its own normalizer included."""
+    table, the class table of its own normalizer included, and with a map (spec.mapped) that
+    normalizer's replacements: tb_uni_count then launches k_uni_count_map."""
 
     def __init__(self, h, spec):
+        maps = {"map1": spec.map1, "map2": spec.map2, "map_rec": spec.map_rec, "map_pool": spec.map_pool}
         super().__init__(h.uni_params, spec, {
             "slots": spec.slots, "pool": spec.pool, "added": spec.added, "cls1": spec.cls1, "cls2": spec.cls2,
-            "aoff": np.array(spec.added_off or [0], dtype=np.int32)})
+            "aoff": np.array(spec.added_off or [0], dtype=np.int32), **(maps if spec.mapped else {})})
 
 
 def declare(lib: ctypes.CDLL) -> None:
@@ -494,7 +496,8 @@ class Kernels:
         return UniTables(native.host(), spec)
 
     def uni_count(self, tabs: UniTables, text, off, n_dev, n_max: int, counts):
-        """k_uni_count: Unigram token counts under bpe_count's contract (csrc/hip/unigram.hip)."""
+        """k_uni_count, or k_uni_count_map for tables with a map: Unigram token counts under
+        bpe_count's contract (csrc/hip/unigram.hip)."""
         if off.numel() < n_max + 1 or counts.numel() < n_max or off.dtype != np.int64 or counts.dtype != np.int32:
             raise DeviceError("uni_count: operand shapes")
         rc = self.lib.tb_uni_count(self.stream(), tabs.block, text.data_ptr(), off.data_ptr(),

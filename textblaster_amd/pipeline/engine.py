@@ -185,7 +185,8 @@ class Engine:
         if backend in ("cuda", "emulate"):
             for i in sorted(self._trailing_tc):
                 spec_fn = getattr(self.tokenizers.get(i), "device_spec", None)
-                spec = spec_fn() if spec_fn is not None else None
+                kw = {"uni_map": True} if self.tune.uni_map else {}
+                spec = spec_fn(**kw) if spec_fn is not None else None
                 if spec is not None:
                     token_counters.append((i, spec))
         if backend == "emulate":

@@ -50,6 +50,9 @@ class DeviceTuning:
     device_resolve: bool = True    # K16: records resolved and outputs compacted on the device
     # trailing TokenCounter steps counted on the device (k_bpe_count, k_bpe_split_count, k_wp_count, k_uni_count)
     device_tokens: bool = True
+    # Unigram tokenizers: the kernel applies the Precompiled normalizer's replacements itself
+    # (k_uni_count_map) instead of handing such documents to the host tokenizer (profiles/unigram_map/)
+    uni_map: bool = False
     device_meta: bool = True       # K18: the output metadata column formatted on the device (profiles/device_meta/)
     dict_marks: bool = True        # dictionary-script docs: host ICU word marks, stay on the device
     c4_line_stats: bool = True     # C4 pass A reads the stage kernels' line export

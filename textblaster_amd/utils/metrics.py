@@ -93,7 +93,7 @@ BPE_HOST_DOCS_TOTAL = Counter("tb_bpe_host_docs_total",
                               "tokenizer with no device counter).", registry=REGISTRY)
 BPE_DEVICE_DOCS_TOTAL = Counter("tb_bpe_device_docs_total",
                                 "Kept documents whose TokenCounter count came from a device kernel (k_bpe_count, "
-                                "k_bpe_split_count, k_wp_count, k_wp_count_fold, k_uni_count).",
+                                "k_bpe_split_count, k_wp_count, k_wp_count_fold, k_uni_count, k_uni_count_map).",
                                 registry=REGISTRY)
 RANK = Gauge("tb_rank", "Data-parallel rank of this process.", registry=REGISTRY)
 WORLD_SIZE = Gauge("tb_world_size", "Number of data-parallel ranks.", registry=REGISTRY)
