@@ -11,7 +11,7 @@
 // One translation unit per kernel family, each with its kernels, its TB_*_WPE register budgets
 // and its extern "C" launchers right below the kernels they launch:
 //
-//  stage.hip     : tb_stage_analyze[_blk]: decode + UAX#29 words + lines + hashes -> Gopher/FineWeb
+//  stage.hip     : tb_stage_analyze[_blk[_mid]]: decode + UAX#29 words + lines + hashes -> Gopher/FineWeb
 //                  records; tb_gr_dup_split: the n-gram orders and duplicated lines of split
 //                  long documents
 //  gr_ngrams.hip : tb_gr_split_wave: the GopherRepetition n-gram fields of the one-wave documents:
@@ -116,7 +116,7 @@ __device__ __forceinline__ const uint8_t* lds_text(DocCtx<P>& x, const uint8_t* 
 #endif
 constexpr int kBlockThreads = TB_BLOCK_THREADS;
 // BlockPar's exchange area (x.par.xs): static LDS of the workgroup kernels that name it, and of no
-// other kernel
+// other kernel (sized for kBlockThreads; a kernel with fewer threads uses its first part)
 __shared__ __attribute__((aligned(16))) char g_block_xs[16 * (kBlockThreads / 64) + 64];
 
 }  // namespace

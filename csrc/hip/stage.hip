@@ -71,6 +71,7 @@ __device__ __forceinline__ void stage_blk_body(
   if (doc >= ndocs || (dead && dead[doc])) return;
   DocCtx<BlockPar<NT>> x =
       make_ctx<BlockPar<NT>>(tabs, pw, pw_n, scratch, scratch_off, doc, (int)blockIdx.x, flags, lds_bytes, prof);
+  static_assert(16 * (NT / 64) + 64 <= (int)sizeof(g_block_xs), "BlockPar<NT>'s exchange area fits g_block_xs");
   x.par.xs = g_block_xs;
   lds_ascii_props(x);
   const uint8_t* b = bytes + off[doc];
@@ -88,8 +89,8 @@ __device__ __forceinline__ void stage_blk_body(
   analyze_stage<BlockPar<NT>, false, kPre>(x, *stage, *plan, LidTables{}, b, n, out);
 }
 
-#define TB_STAGE_BLK_KERNEL(NAME, NT, PRE)                                                             \
-  __global__ __launch_bounds__(NT) TB_BLK_ATTR void NAME(                                            \
+#define TB_STAGE_BLK_KERNEL(NAME, NT, PRE, ATTR)                                                       \
+  __global__ __launch_bounds__(NT) ATTR void NAME(                                                   \
       const DevPlan* __restrict__ plan, const DevStage* __restrict__ stage, const uint8_t* __restrict__ bytes, \
       const int64_t* __restrict__ off, const int32_t* __restrict__ perm, int32_t ndocs, char* scratch,         \
       const int64_t* __restrict__ scratch_off, const uint64_t* __restrict__ pw, uint32_t pw_n, DevTables tabs,  \
@@ -99,9 +100,29 @@ __device__ __forceinline__ void stage_blk_body(
     stage_blk_body<NT, PRE>(plan, stage, bytes, off, perm, ndocs, scratch, scratch_off, pw, pw_n, tabs, rec, flags, \
                        lds_bytes, prof, dead, gr_export, n_split, split_bytes, line_stats, pre, n_pre, dict); \
   }
-TB_STAGE_BLK_KERNEL(k_stage_analyze_blk, kBlockThreads, false)
+TB_STAGE_BLK_KERNEL(k_stage_analyze_blk, kBlockThreads, false, TB_BLK_ATTR)
 // documents with a pre-pass (tb_stage_analyze_blk with `pre`): every launch position has one
-TB_STAGE_BLK_KERNEL(k_stage_analyze_blk_pre, kBlockThreads, true)
+TB_STAGE_BLK_KERNEL(k_stage_analyze_blk_pre, kBlockThreads, true, TB_BLK_ATTR)
+
+// Mid-sized workgroup documents (tb_stage_analyze_blk_mid; the caller picks them by length): the
+// same body with kBlockMidThreads threads and a register budget of its own. At 4-32 KB the kernel
+// is bound by the latency of one document's chain of passes, not by its spills or its thread
+// count: with three documents per CU (48 KB slices) 256 threads take as long per document as 512
+// (spill-free at 3 waves/SIMD, 168 VGPRs: 2.82 against 2.75 ms per step for both stages). What
+// pays is more documents per CU, which four waves per document allow: five 31 KB slices at
+// 5 waves/SIMD (96 VGPRs, 134 spilled) 2.47 ms; four at 4 waves 2.52, six at 6 waves 2.60, eight
+// at 8 waves 3.16 (profiles/blk_mid/). TB_BLK_MID_WPE=k builds another budget (0: none) for A/B
+// runs; the LDS slice is the caller's (pipeline/device.py MID_LDS_BYTES).
+#ifndef TB_BLK_MID_WPE
+#define TB_BLK_MID_WPE 5
+#endif
+#if TB_BLK_MID_WPE > 0
+#define TB_BLK_MID_ATTR __attribute__((amdgpu_waves_per_eu(TB_BLK_MID_WPE, 8)))
+#else
+#define TB_BLK_MID_ATTR
+#endif
+constexpr int kBlockMidThreads = 256;
+TB_STAGE_BLK_KERNEL(k_stage_analyze_blk_mid, kBlockMidThreads, false, TB_BLK_MID_ATTR)
 
 }  // namespace
 
@@ -153,6 +174,27 @@ int tb_stage_analyze_blk(hipStream_t stream, const void* plan, const void* stage
                      (const DevStage*)stage, d->bytes, d->off, d->perm, d->ndocs, w->scratch, w->scratch_off, tb->pw,
                      tb->pw_n, tb->ucd, w->rec, w->flags, lds_bytes, w->prof, d->dead, (GrExport*)gr_export, n_split,
                      split_bytes, line_stats, (const PreDoc*)pre, pre ? nblocks : 0, dict ? *dict : DictIn{});
+  return (int)hipGetLastError();
+}
+
+// The same launch with kBlockMidThreads threads per document (k_stage_analyze_blk_mid), for the
+// shorter workgroup documents. It has no pre-pass build; split documents may take it like the
+// other one.
+int tb_stage_analyze_blk_mid(hipStream_t stream, const void* plan, const void* stage, const TbDocs* d,
+                             const TbWork* w, const TbTables* tb, void* gr_export, int32_t n_split,
+                             uint32_t split_bytes, uint32_t* line_stats, const DictIn* dict) {
+  const int32_t nblocks = d->n_launch;
+  const uint32_t lds_bytes = w->lds_bytes;
+  if (nblocks <= 0) return 0;
+  if (!d->perm || lds_bytes > kMaxLdsPerBlk || n_split < 0 || n_split > nblocks) return (int)hipErrorInvalidValue;
+  if (lds_bytes > 65536)
+    (void)hipFuncSetAttribute((const void*)k_stage_analyze_blk_mid, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+  hipLaunchKernelGGL(k_stage_analyze_blk_mid, dim3(nblocks), dim3(kBlockMidThreads), lds_bytes, stream,
+                     (const DevPlan*)plan, (const DevStage*)stage, d->bytes, d->off, d->perm, d->ndocs, w->scratch,
+                     w->scratch_off, tb->pw, tb->pw_n, tb->ucd, w->rec, w->flags, lds_bytes, w->prof, d->dead,
+                     (GrExport*)gr_export, n_split, split_bytes, line_stats, (const PreDoc*)nullptr, 0,
+                     dict ? *dict : DictIn{});
   return (int)hipGetLastError();
 }
 

@@ -103,6 +103,8 @@ _SIGS = {
     "tb_stage_analyze": [_P, _P, _P, _DOCS, _WORK, _TAB, _P, _P, ctypes.POINTER(DictIn)],
     # stream, plan, stage, docs, work, tables, gr_export, n_split, split_bytes, line_stats, pre, dict_in
     "tb_stage_analyze_blk": [_P, _P, _P, _DOCS, _WORK, _TAB, _P, _I32, _U32, _P, _P, ctypes.POINTER(DictIn)],
+    # (the same without pre)
+    "tb_stage_analyze_blk_mid": [_P, _P, _P, _DOCS, _WORK, _TAB, _P, _I32, _U32, _P, ctypes.POINTER(DictIn)],
     # stream, stage, gr_step, docs, n_tasks, gr_export, work, tables, (block, n_big | cursor)
     "tb_gr_split_wave": [_P, _P, _I32, _DOCS, _I32, _P, _WORK, _TAB, _I32, _I32],
     "tb_gr_dup_split": [_P, _P, _I32, _DOCS, _I32, _P, _WORK, _TAB, _P],
@@ -317,18 +319,26 @@ class Kernels:
         _check(rc, "tb_gr_split_wave")
 
     def stage_analyze_blk(self, plan, stage, docs: Docs, work: Work, tables: Tables, gr_export=None, n_split=0,
-                          split_bytes=0, line_stats=None, pre=None, dict_in: Optional[DictIn] = None):
+                          split_bytes=0, line_stats=None, pre=None, dict_in: Optional[DictIn] = None, mid=False):
         """k_stage_analyze_blk; ``gr_export`` (zeroed, >= n_split descriptors): the first n_split
         launch positions longer than ``split_bytes`` export their word arrays (split mode);
-        ``pre``: the pre-pass descriptors of every launched document."""
+        ``pre``: the pre-pass descriptors of every launched document. ``mid``: the 256-thread
+        build for mid-sized documents (k_stage_analyze_blk_mid; it has no pre-pass variant)."""
         if gr_export is not None and gr_export.nbytes < n_split * self.sizeof_gr_export:
             raise DeviceError("stage_analyze_blk: export buffer too small")
         if not 0 <= n_split <= docs.n_launch:
             raise DeviceError("stage_analyze_blk: n_split out of range")
-        rc = self.lib.tb_stage_analyze_blk(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work, tables,
-                                           _ptr(gr_export), n_split if gr_export is not None else 0, split_bytes,
-                                           _ptr(line_stats), _ptr(pre), dict_in)
-        _check(rc, "tb_stage_analyze_blk")
+        ns = n_split if gr_export is not None else 0
+        if mid:
+            if pre is not None:
+                raise DeviceError("stage_analyze_blk: the mid-size kernel takes no pre-pass documents")
+            rc = self.lib.tb_stage_analyze_blk_mid(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work,
+                                                   tables, _ptr(gr_export), ns, split_bytes, _ptr(line_stats),
+                                                   dict_in)
+        else:
+            rc = self.lib.tb_stage_analyze_blk(self.stream(), plan.data_ptr(), stage.data_ptr(), docs, work, tables,
+                                               _ptr(gr_export), ns, split_bytes, _ptr(line_stats), _ptr(pre), dict_in)
+        _check(rc, "tb_stage_analyze_blk_mid" if mid else "tb_stage_analyze_blk")
 
     def pre_decode(self, docs: Docs, pre, tiles_max, cnt, tables: Tables):
         """k_pre_count / k_pre_decode / k_pre_wb: code points and word-break marks of

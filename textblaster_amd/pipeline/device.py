@@ -260,6 +260,27 @@ def lds_doc_slices(lens: np.ndarray, long_doc_bytes: int, per_byte: float, fixed
     return out
 
 
+# A batch whose workgroup documents are all at most this long (none is split; pre-pass documents
+# apart) runs them in the 256-thread stage kernel (k_stage_analyze_blk_mid, csrc/hip/stage.hip),
+# five to a CU: its register budget is 5 waves/SIMD and its LDS slice 31 KB. All or none: the two
+# kernels share a stream, so a batch split between them pays the tail of both launches and loses
+# (8 and 16 KB thresholds on the headline batch, BASELINE config 5: profiles/blk_mid/). 0: never.
+MID_DOC_BYTES = 32768
+MID_LDS_BYTES = 31744  # 0: lds_bytes_blk
+
+
+def blk_mid_count(long_lens: np.ndarray, n_pre: int, n_split: int, mid_doc_bytes: int) -> int:
+    """How many of the workgroup documents take the mid-size stage kernel: ``long_lens`` are the
+    lengths of launch positions [0, n_long), longest first, the first ``n_pre`` with a pre-pass,
+    the first ``n_split`` holding every split document. All of [n_pre, n_long) when none of them
+    is split or longer than ``mid_doc_bytes``, else none (the full-size kernel takes them all).
+    ``mid_doc_bytes`` <= 0: none."""
+    tail = np.asarray(long_lens[max(n_pre, 0):])
+    if mid_doc_bytes <= 0 or len(tail) == 0 or n_split > n_pre or bool(np.any(tail > mid_doc_bytes)):
+        return 0
+    return int(len(tail))
+
+
 class _Slot:
     """Per in-flight batch resources: pinned input staging buffer and device scratch arena.
     Two slots alternate, so batch k+1 can be staged and launched while batch k's results are
@@ -1082,16 +1103,20 @@ class DeviceRunner:
             if ver == 0 and b.pre_v0 is None:
                 b.pre_v0 = self._pre_decode(b, vb, vo, skip)
             pre, n_pre = b.pre_v0 if ver == 0 else (None, 0)
-            # launch positions [0, n_pre): the pre-pass kernel instantiation, the rest the common one
-            for a0, a1, with_pre in ((0, n_pre, True), (n_pre, n_long, False)):
+            # launch positions [0, n_pre): the pre-pass kernel instantiation, the rest the common
+            # one, or the mid-size one when all of them are mid-sized (n_mid: all or none)
+            n_mid = blk_mid_count(b.lens_perm[:n_long], n_pre, n_split, MID_DOC_BYTES)
+            for a0, a1, with_pre, mid in ((0, n_pre, True, False), (n_pre, n_long - n_mid, False, False),
+                                          (n_long - n_mid, n_long, False, True)):
                 if a1 <= a0:
                     continue
                 ns = max(0, min(n_split, a1) - a0)
                 self.k.stage_analyze_blk(
                     self.plan_t, self.stage_ts[s], Docs.of(vb, vo, b.d_perm[a0:a1], a1 - a0, ndocs, skip),
-                    Work.of(b.scratch, b.d_soff[a0:], rec, b.flags, self.lds_bytes_blk, prof), b.tables,
+                    Work.of(b.scratch, b.d_soff[a0:], rec, b.flags,
+                            (MID_LDS_BYTES if mid else 0) or self.lds_bytes_blk, prof), b.tables,
                     gx[a0 * esz:] if (gx is not None and ns) else None, ns, self.split_doc_bytes, ls_out,
-                    pre if with_pre else None, b.dict_in.get(ver))
+                    pre if with_pre else None, b.dict_in.get(ver), mid=mid)
             if n_split:
                 gr_pos, n_tasks = self.gr_split[s]
                 cur = rt.empty(1, np.uint32)
