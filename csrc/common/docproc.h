@@ -2140,23 +2140,38 @@ TB_HD bool ci_starts_with(const uint8_t* b, uint32_t n, const char* pat, int ple
   return true;
 }
 
-// The first three bytes at b (n available), ASCII-lowercased, little endian (0 past the end):
-// three independent loads. Every C4 phrase starts with three ASCII letters other than 'k' (the
-// only pattern letter with a multi-byte match, the Kelvin sign), so a phrase can only match where
-// this equals its packed prefix.
-TB_HD uint32_t lower3(const uint8_t* b, uint32_t n) {
-  uint32_t w = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 3; ++k) {
-    uint32_t c = k < n ? b[k] : 0u;
-    if (c >= 'A' && c <= 'Z') c += 32;
-    w |= c << (8 * k);
+// ASCII 'A'..'Z' -> 'a'..'z' in all 8 bytes of v (other bytes unchanged).
+TB_HD uint64_t swar_lower8(uint64_t v) {
+  constexpr uint64_t k7F = 0x7F7F7F7F7F7F7F7Full, k80 = 0x8080808080808080ull;
+  const uint64_t ge_a = (v & k7F) + 0x3F3F3F3F3F3F3F3Full;  // bit 7 set: byte & 0x7F >= 'A'
+  const uint64_t gt_z = (v & k7F) + 0x2525252525252525ull;  // bit 7 set: byte & 0x7F > 'Z'
+  const uint64_t upper = ge_a & ~gt_z & ~v & k80;
+  return v | (upper >> 2);
+}
+
+// The four bytes b[q, q + 4) of the text b[0, n), little endian, for a position q at which b + q
+// is dword aligned; bytes outside [0, n) read as zero. Only a dword that lies wholly inside the
+// text is loaded as one: the first and last dwords of a text's aligned span are read byte by
+// byte, since the bytes around a text need not be readable (the last document of a batch, a
+// host buffer sized to the text).
+TB_HD uint32_t text_dword(const uint8_t* b, uint32_t n, int64_t q) {
+  if (q >= 0 && q + 4 <= (int64_t)n) return *(const uint32_t*)(b + q);
+  uint32_t v = 0;
+  for (uint32_t j = 0; j < 4; ++j) {
+    const int64_t sj = q + j;
+    if (sj >= 0 && sj < (int64_t)n) v |= (uint32_t)b[sj] << (8 * j);
   }
-  return w;
+  return v;
 }
-TB_HD constexpr uint32_t pack3(const char* p) {
-  return (uint32_t)(uint8_t)p[0] | ((uint32_t)(uint8_t)p[1] << 8) | ((uint32_t)(uint8_t)p[2] << 16);
+
+// Up to eight bytes of the string p[0, len) from index `from`, packed little endian.
+TB_HD constexpr uint64_t pack_le(const char* p, int len, int from = 0) {
+  uint64_t v = 0;
+  for (int k = 0; k < 8 && from + k < len; ++k) v |= (uint64_t)(uint8_t)p[from + k] << (8 * k);
+  return v;
 }
+TB_HD constexpr uint32_t pack3(const char* p) { return (uint32_t)pack_le(p, 3); }
+TB_HD constexpr uint64_t pack5(const char* p) { return pack_le(p, 5); }
 
 // Bits of the per-line pattern flags (c4_pass_a)
 enum : uint32_t { C4F_JS = 1, C4F_POLICY = 2 };
@@ -2165,27 +2180,86 @@ enum : uint32_t { C4F_JS = 1, C4F_POLICY = 2 };
 // citation, and whether a javascript / policy phrase starts anywhere (C4F_JS / C4F_POLICY).
 enum : uint32_t { C4S_LOREM = 4, C4S_CURLY = 8, C4S_CITE = 16 };
 
-// The pattern bits (C4F_JS | C4F_POLICY) of the phrases starting at byte s (case-folded).
-TB_HD uint32_t c4_phrases_at(const DevC4& c4, const uint8_t* b, uint32_t n, uint32_t s) {
-  uint8_t c0 = b[s];
-  if (c0 >= 'A' && c0 <= 'Z') c0 = (uint8_t)(c0 + 32);
-  if (c0 != 'j' && c0 != 't' && c0 != 'p' && c0 != 'c' && c0 != 'u') return 0;
-  const char* const kPol[6] = {"terms of use", "privacy policy", "cookie policy",
-                               "uses cookies", "use of cookies", "use cookies"};
-  const int kPolLen[6] = {12, 14, 13, 12, 14, 11};
-  uint32_t bits = 0;
-  const uint32_t w3 = lower3(b + s, n - s);
-  auto pre = [&](const char* pat) { return w3 == pack3(pat); };
-  if (c4.filter_javascript && c0 == 'j' && pre("javascript") && ci_starts_with(b + s, n - s, "javascript", 10))
-    bits |= C4F_JS;
-  if (c4.filter_policy)
-    for (int t = 0; t < 6; ++t)
-      if (kPol[t][0] == (char)c0 && pre(kPol[t]) && ci_starts_with(b + s, n - s, kPol[t], kPolLen[t])) {
-        bits |= C4F_POLICY;
-        break;
-      }
-  return bits;
+// The 16 bytes of the text b[0, n) from byte s, ASCII-lowercased, little endian in lo and hi
+// (zero past the end): the five aligned dwords that hold them, loaded together and shifted into
+// place.
+TB_HD void lower16_at(const uint8_t* b, uint32_t n, uint32_t s, uint64_t& lo, uint64_t& hi) {
+  const uint32_t sh = (uint32_t)((uintptr_t)(b + s) & 3u);
+  const int64_t q = (int64_t)s - sh;
+  uint32_t d[5];
+#pragma unroll
+  for (uint32_t k = 0; k < 5; ++k) d[k] = text_dword(b, n, q + 4 * k);
+  const uint64_t w0 = (uint64_t)d[0] | ((uint64_t)d[1] << 32), w1 = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
+  uint64_t v0 = w0, v1 = w1;
+  if (sh) {
+    v0 = (w0 >> (8 * sh)) | (w1 << (64 - 8 * sh));
+    v1 = (w1 >> (8 * sh)) | ((uint64_t)d[4] << (64 - 8 * sh));
+  }
+  lo = swar_lower8(v0);
+  hi = swar_lower8(v1);
 }
+
+// Does the phrase pat (len bytes, 9 <= len <= 16; plo / phi: its bytes packed) start at byte s,
+// case-folded as ci_starts_with folds? lo / hi are lower16_at(b, n, s). kpos: the index of the
+// phrase's 'k' (-1: none). A Kelvin sign there is three bytes long and moves the rest of the
+// phrase, so only a window whose first difference is 0xE2 at kpos goes to the byte-wise test.
+TB_HD bool c4_phrase_eq(const uint8_t* b, uint32_t n, uint32_t s, uint64_t lo, uint64_t hi, uint64_t plo,
+                        uint64_t phi, int len, int kpos, const char* pat) {
+  const uint64_t xl = lo ^ plo;
+  const uint64_t xh = (hi ^ phi) & (~0ull >> (64 - 8 * (len - 8)));
+  if ((xl | xh) == 0) return true;
+  if (kpos < 0) return false;
+  const int j = xl ? (__builtin_ctzll(xl) >> 3) : 8 + (__builtin_ctzll(xh) >> 3);
+  if (j != kpos) return false;
+  const uint32_t c = (uint32_t)((kpos < 8 ? lo >> (8 * kpos) : hi >> (8 * (kpos - 8))) & 0xFFu);
+  return c == 0xE2 && ci_starts_with(b + s, n - s, pat, len);
+}
+#define TB_C4_PHRASE_EQ(pat, kpos) \
+  c4_phrase_eq(b, n, s, lo, hi, pack_le(pat, sizeof(pat) - 1), pack_le(pat, sizeof(pat) - 1, 8), \
+               (int)sizeof(pat) - 1, kpos, pat)
+
+// The pattern bits (C4F_JS | C4F_POLICY) of the phrases starting at byte s (case-folded). lw holds
+// the lowercased bytes from s, at least five of them (scan_bytes16). Every phrase starts with
+// ASCII letters and spaces other than 'k' (the only pattern letter with a multi-byte match, the
+// Kelvin sign) up to its fifth byte, "cookie policy" up to its third: a phrase can only match
+// where lw starts with its prefix, and a text almost never holds one of these prefixes without
+// the phrase. Only such a position loads its 16 bytes and compares them to the packed phrase.
+TB_HD uint32_t c4_phrases_at(const DevC4& c4, const uint8_t* b, uint32_t n, uint32_t s, uint64_t lw) {
+  const uint64_t p5 = lw & 0xFFFFFFFFFFull;
+  const uint32_t c3 = (uint32_t)(lw >> 24) & 0xFFu;
+  int t;
+  if (p5 == pack5("terms")) t = 1;
+  else if (p5 == pack5("use c")) t = 6;
+  else if (p5 == pack5("use o")) t = 5;
+  else if (p5 == pack5("uses ")) t = 4;
+  else if (p5 == pack5("priva")) t = 2;
+  else if (p5 == pack5("javas")) t = 0;
+  else if (((uint32_t)lw & 0xFFFFFFu) == pack3("coo") && (c3 == 'k' || c3 == 0xE2)) t = 3;
+  else return 0;
+  if (t == 0 ? !c4.filter_javascript : !c4.filter_policy) return 0;
+  uint64_t lo, hi;
+  lower16_at(b, n, s, lo, hi);
+  bool hit;
+  switch (t) {
+    case 0: hit = TB_C4_PHRASE_EQ("javascript", -1); break;
+    case 1: hit = TB_C4_PHRASE_EQ("terms of use", -1); break;
+    case 2: hit = TB_C4_PHRASE_EQ("privacy policy", -1); break;
+    case 3: hit = TB_C4_PHRASE_EQ("cookie policy", 3); break;
+    case 4: hit = TB_C4_PHRASE_EQ("uses cookies", 8); break;
+    case 5: hit = TB_C4_PHRASE_EQ("use of cookies", 10); break;
+    default: hit = TB_C4_PHRASE_EQ("use cookies", 7); break;
+  }
+  return hit ? (t == 0 ? C4F_JS : C4F_POLICY) : 0u;
+}
+
+// Does "lorem ipsum" start at byte s (case-folded)? lw as for c4_phrases_at.
+TB_HD bool c4_lorem_at(const uint8_t* b, uint32_t n, uint32_t s, uint64_t lw) {
+  if ((lw & 0xFFFFFFFFFFull) != pack5("lorem")) return false;
+  uint64_t lo, hi;
+  lower16_at(b, n, s, lo, hi);
+  return TB_C4_PHRASE_EQ("lorem ipsum", -1);
+}
+#undef TB_C4_PHRASE_EQ
 
 // Bytes of v equal to c: bit 7 of each such byte set (exact, no carries between bytes).
 TB_HD uint32_t swar_eq_mask(uint32_t v, uint32_t c) {
@@ -2248,17 +2322,9 @@ TB_HD uint64_t gq_byte_counts(DocCtx<P>& x, const uint8_t* b, uint32_t n) {
   });
 }
 
-// ASCII 'A'..'Z' -> 'a'..'z' in all 8 bytes of v (other bytes unchanged).
-TB_HD uint64_t swar_lower8(uint64_t v) {
-  constexpr uint64_t k7F = 0x7F7F7F7F7F7F7F7Full, k80 = 0x8080808080808080ull;
-  const uint64_t ge_a = (v & k7F) + 0x3F3F3F3F3F3F3F3Full;  // bit 7 set: byte & 0x7F >= 'A'
-  const uint64_t gt_z = (v & k7F) + 0x2525252525252525ull;  // bit 7 set: byte & 0x7F > 'Z'
-  const uint64_t upper = ge_a & ~gt_z & ~v & k80;
-  return v | (upper >> 2);
-}
-
-// Every byte position s of b[0, n) visited as f(s, c0, c1, l3): its byte, the next one (0 past the
-// end) and the three bytes from s ASCII-lowercased (l3, little endian). Items are four aligned
+// Every byte position s of b[0, n) visited as f(s, c0, c1, lw): its byte, the next one (0 past the
+// end) and lw, the bytes from s to the end of its 8-byte window ASCII-lowercased (little endian,
+// five to eight of them, zero past the text and above them). Items are four aligned
 // dwords whose five loads (one of look-ahead) are issued together, and the lowercase windows
 // come from SWAR shifts: one memory round trip per 16 bytes, no per-byte loads.
 template <class P, class F>
@@ -2267,16 +2333,8 @@ TB_HD void scan_bytes16(DocCtx<P>& x, const uint8_t* b, uint32_t n, F&& f) {
   const uint32_t head = (uint32_t)((uintptr_t)b - a0);
   const uint32_t nd = (head + n + 3) >> 2;
   const uint32_t* w = (const uint32_t*)a0;
-  auto dw = [&](uint32_t k) -> uint32_t {  // dword k of the aligned stream, bytes past the text zero
-    if (k >= nd) return 0u;
-    const int64_t e = (int64_t)4 * k + 4 - head;  // doc position one past its last byte
-    if (e <= (int64_t)n && 4 * k >= head) return w[k];
-    uint32_t v = 0;
-    for (uint32_t j = 0; j < 4; ++j) {
-      const int64_t sj = (int64_t)4 * k + j - head;
-      if (sj >= 0 && sj < (int64_t)n) v |= (uint32_t)b[sj] << (8 * j);
-    }
-    return v;
+  auto dw = [&](uint32_t k) -> uint32_t {  // dword k of the aligned stream, bytes outside the text zero
+    return k < nd ? text_dword(b, n, (int64_t)4 * k - head) : 0u;
   };
   x.par.for_n((nd + 3) >> 2, [&](uint32_t g) {
     uint32_t d[5];
@@ -2291,31 +2349,32 @@ TB_HD void scan_bytes16(DocCtx<P>& x, const uint8_t* b, uint32_t n, F&& f) {
         const int64_t sp = (int64_t)4 * k + r - head;
         if (sp < 0 || sp >= (int64_t)n) continue;
         f((uint32_t)sp, (uint32_t)(v >> (8 * r)) & 0xFFu, (uint32_t)(v >> (8 * r + 8)) & 0xFFu,
-          (uint32_t)(lo >> (8 * r)) & 0xFFFFFFu);
+          lo >> (8 * r));
       }
     }
   });
 }
 
-// Could a javascript / policy phrase start here (its case-folded 3-byte prefix)?
-TB_HD bool c4_phrase_prefix(uint32_t l3) {
+// Could a javascript / policy phrase start here (its case-folded 3-byte prefix)? The cheap first
+// test of every position; c4_phrases_at goes on with the longer prefix.
+TB_HD bool c4_phrase_prefix(uint64_t lw) {
+  const uint32_t l3 = (uint32_t)lw & 0xFFFFFFu;
   return l3 == pack3("jav") || l3 == pack3("ter") || l3 == pack3("pri") || l3 == pack3("coo") || l3 == pack3("use");
 }
 
 // One pass over the bytes: lorem ipsum and curly brackets (lowercase().contains("lorem ipsum") ==
 // the pattern starts, case-folded, at some 'l'), a possible citation ('[' followed by a digit:
 // a non-ASCII byte after the '[' counts too, so the test is conservative) and the phrase bits;
-// only a position whose 3-byte prefix matches runs the exact comparison (ci_starts_with).
+// only a position whose 5-byte prefix matches runs the exact comparison (c4_phrase_eq).
 template <class P>
 TB_HD uint32_t c4_byte_scan(DocCtx<P>& x, const DevC4& c4, const uint8_t* b, uint32_t n) {
   uint32_t acc = 0;
   const bool phrases = c4.filter_javascript || c4.filter_policy;
-  scan_bytes16(x, b, n, [&](uint32_t s, uint32_t c0, uint32_t c1, uint32_t l3) {
+  scan_bytes16(x, b, n, [&](uint32_t s, uint32_t c0, uint32_t c1, uint64_t lw) {
     if (c4.filter_curly_bracket && (c0 == '{' || c0 == '}')) acc |= C4S_CURLY;
     if (c0 == '[' && ((c1 >= '0' && c1 <= '9') || c1 >= 0x80)) acc |= C4S_CITE;
-    if (c4.filter_lorem_ipsum && l3 == pack3("lor") && ci_starts_with(b + s, n - s, "lorem ipsum", 11))
-      acc |= C4S_LOREM;
-    if (phrases && c4_phrase_prefix(l3)) acc |= c4_phrases_at(c4, b, n, s);
+    if (c4.filter_lorem_ipsum && c4_lorem_at(b, n, s, lw)) acc |= C4S_LOREM;
+    if (phrases && c4_phrase_prefix(lw)) acc |= c4_phrases_at(c4, b, n, s, lw);
   });
   return x.par.reduce_or(acc);
 }
@@ -2392,9 +2451,9 @@ TB_HD void c4_plain_tail(DocCtx<P>& x, const DevC4& c4, const uint8_t* b, uint32
     // only when the byte scan saw a phrase somewhere (rare). A phrase (letters and spaces, starting
     // with a letter) that matches at a byte lies inside one line's trimmed span: it cannot cross
     // the line feed or run into trailing whitespace.
-    scan_bytes16(x, b, n, [&](uint32_t s, uint32_t, uint32_t, uint32_t l3) {
-      if (!c4_phrase_prefix(l3)) return;
-      const uint32_t bits = c4_phrases_at(c4, b, n, s);
+    scan_bytes16(x, b, n, [&](uint32_t s, uint32_t, uint32_t, uint64_t lw) {
+      if (!c4_phrase_prefix(lw)) return;
+      const uint32_t bits = c4_phrases_at(c4, b, n, s, lw);
       if (bits) P::or32(&pf[line_of_byte(s)], bits);
     });
     x.par.sync();
@@ -2670,9 +2729,9 @@ TB_HD bool c4_pass_a_cite_export(DocCtx<P>& x, const DevC4& c4, const uint8_t* b
   }
   x.stamp(PH_C4_WORDS);
   if (c4.filter_javascript || c4.filter_policy) {
-    scan_bytes16(x, Pb, Ptot, [&](uint32_t s, uint32_t, uint32_t, uint32_t l3) {
-      if (!c4_phrase_prefix(l3)) return;
-      const uint32_t bits = c4_phrases_at(c4, Pb, Ptot, s);
+    scan_bytes16(x, Pb, Ptot, [&](uint32_t s, uint32_t, uint32_t, uint64_t lw) {
+      if (!c4_phrase_prefix(lw)) return;
+      const uint32_t bits = c4_phrases_at(c4, Pb, Ptot, s, lw);
       if (bits) P::or32(&pf[line_of_p(s)], bits);
     });
   }
@@ -2998,9 +3057,9 @@ TB_HD void c4_pass_a(DocCtx<P>& x, const DevC4& c4, const uint8_t* b, uint32_t n
   if (c4.filter_javascript || c4.filter_policy) {
     // The phrases hold letters and spaces only, so a match never runs over the '\n' that ends
     // its line: match against the rest of Pb first, look the line up only on a match.
-    scan_bytes16(x, Pb, Ptot, [&](uint32_t s, uint32_t, uint32_t, uint32_t l3) {
-      if (!c4_phrase_prefix(l3)) return;
-      const uint32_t bits = c4_phrases_at(c4, Pb, Ptot, s);
+    scan_bytes16(x, Pb, Ptot, [&](uint32_t s, uint32_t, uint32_t, uint64_t lw) {
+      if (!c4_phrase_prefix(lw)) return;
+      const uint32_t bits = c4_phrases_at(c4, Pb, Ptot, s, lw);
       if (bits) P::or32(&pf[line_of_byte(s)], bits);
     });
   }
