@@ -36,6 +36,9 @@ def test_device_run_equals_cpu_oracle(tmp_path):
     (sg, og, eg), (sc, oc, ec) = outs["cuda"], outs["cpu"]
     assert (sg.docs, sg.kept, sg.excluded, sg.errors) == (sc.docs, sc.kept, sc.excluded, sc.errors)
     assert sg.step_filtered == sc.step_filtered
+    # every document was decided on the device (the CJK one fails the language gate there): the
+    # CPU path is the oracle's own code
+    assert sg.delegated == 0
     assert og.column("id").equals(oc.column("id")) and og.column("text").equals(oc.column("text"))
     assert eg.column("id").equals(ec.column("id")) and eg.column("text").equals(ec.column("text"))
     # metadata (with the language confidence) identical, key order aside
@@ -139,6 +142,10 @@ def test_device_equals_icu_oracle_on_hard_corpus(monkeypatch, mode):
         assert eng.device_runner.gr_split and eng.device_runner.split_doc_bytes <= 4608
     a = eng.process(data, off)
     b = Engine(cfg, backend="cpu", segmentation="icu", keep_reasons=True).process(data, off)
+    # every document is decided on the device: the two dictionary-script documents (EDGE) fail the
+    # language gate there, and nothing else may go to the CPU path, which is the oracle's own code
+    assert [i for i, t in enumerate(texts) if eng.h.has_dict_script(t)] == [1512, 1513]
+    assert a.n_delegated == 0
     np.testing.assert_array_equal(a.status, b.status)
     np.testing.assert_array_equal(a.fail_step, b.fail_step)
     assert a.reasons.keys() == b.reasons.keys()

@@ -21,8 +21,7 @@ EDGE = ["", "   ", "\n\n", "a", "a\r\nb\r\n", "Hello.\n\n\nHello.\n\nHello.", "x
         "a b a b a b a b a b a b a b", "ab c a bc ab c a bc"]
 
 
-@pytest.fixture(scope="module")
-def corpus():
+def kernels_corpus():
     # adversarial documents (UAX#29 fuzz pool, constructs across the 64-item chunk boundaries)
     texts = synth.make_corpus(3000, 1024, seed=11) + EDGE + adversarial_corpus()
     rng = np.random.default_rng(7)
@@ -34,6 +33,31 @@ def corpus():
              "JavaScript must be enabled. Short one...\nThe quick brown fox jumps over the lazy dog.\n") * 200
     texts += [c4ish, c4ish.replace("\n", " ")]
     return texts
+
+
+@pytest.fixture(scope="module")
+def corpus():
+    return kernels_corpus()
+
+
+DOC_NEEDS_CPU, DOC_OVERFLOW = 1, 2  # docproc.h
+
+
+def _dict_docs(host, vd, vo):
+    """Per document of a content version: does it hold a dictionary script (CJK, Thai, ...)? The bare
+    emulation calls of this module supply no host ICU word marks, so on the emulation's side exactly
+    these documents are flagged (DOC_NEEDS_CPU) and leave a comparison; nothing else does."""
+    vd = np.asarray(vd)
+    return np.array([host.has_dict_script(bytes(vd[vo[d]:vo[d + 1]]).decode("utf-8", errors="replace"))
+                     for d in range(len(vo) - 1)], dtype=bool)
+
+
+def _assert_flags(flags, expected, texts):
+    """The device's flag vector, whole: a kernel that flags a document it should analyse (or
+    overflows its arena) does not pass by having the document masked out."""
+    flags = np.asarray(flags)
+    bad = np.nonzero(flags != np.asarray(expected, dtype=flags.dtype))[0]
+    assert len(bad) == 0, [(int(d), int(flags[d]), len(texts[d]), texts[d][:60]) for d in bad[:8]]
 
 
 @pytest.fixture(scope="module")
@@ -58,6 +82,9 @@ def test_device_records_match_host_emulation(host, corpus, runner_parts):
     data, off = synth.pack(corpus)
     res = runner.run(data, off)
     n = len(corpus)
+    # the device flags nothing: the host's ICU marks keep the dictionary-script documents on it
+    assert runner.dict_marks
+    _assert_flags(res.flags, np.zeros(n), corpus)
     # documents a gate skipped in a pass (csrc/common/gate.h) have zero records there
     def live(step_i):
         p = runner.pass_of_step[step_i]
@@ -68,12 +95,16 @@ def test_device_records_match_host_emulation(host, corpus, runner_parts):
         vd, vo = (data, off) if ver == 0 else res.versions[ver]
         ref, rflags = host.emulate_stage(steps, idx, np.ascontiguousarray(vd), np.ascontiguousarray(vo), 8,
                                          lid.native())
+        dict_v = _dict_docs(host, vd, vo)
+        assert np.array_equal(rflags, np.where(dict_v, DOC_NEEDS_CPU, 0)), np.nonzero((rflags != 0) != dict_v)[0][:8]
         got = res.stage_recs[s]
         width_total, layout = runner.stage_layout[s]
         for (kind, width, prefix), step_i in sorted(zip(layout, idx), key=lambda t: t[0][0] == 4):
             a = got[prefix * n:(prefix + width) * n].reshape(n, width)
             b = ref[prefix * n:(prefix + width) * n].reshape(n, width)
             ok = (res.flags == 0) & (rflags == 0) & live(step_i)
+            # floor: every document the gates left in this pass is compared, bar the predicted set
+            assert np.count_nonzero(ok) == n - np.count_nonzero(~live(step_i)) - np.count_nonzero(dict_v & live(step_i))
             if kind == 4:
                 # language id: exact integer n-gram sums on both sides, so the language is equal;
                 # the f64 softmax may differ in the last ulp of exp (device libm vs host)
@@ -89,7 +120,10 @@ def test_device_records_match_host_emulation(host, corpus, runner_parts):
         ver = plan.steps[i].version_in
         vd, vo = (data, off) if ver == 0 else res.versions[ver]
         rrec, rdata, roff, rflags = host.emulate_c4(steps[i], np.ascontiguousarray(vd), np.ascontiguousarray(vo), 8)
+        dict_v = _dict_docs(host, vd, vo)
+        assert np.array_equal(rflags, np.where(dict_v, DOC_NEEDS_CPU, 0)), np.nonzero((rflags != 0) != dict_v)[0][:8]
         ok = (res.flags == 0) & (rflags == 0) & live(i)
+        assert np.count_nonzero(ok) == n - np.count_nonzero(~live(i)) - np.count_nonzero(dict_v & live(i))
         assert np.array_equal(res.c4_recs[i].reshape(n, 7)[ok], rrec.reshape(n, 7)[ok])
         gd, go = res.versions[plan.steps[i].version_out]
         for d in np.nonzero(ok)[0]:
@@ -104,10 +138,17 @@ def test_device_gate_matches_host_gate(host, corpus, runner_parts):
     cfg, steps, plan, runner, lid = runner_parts
     data, off = synth.pack(corpus)
     res = runner.run(data, off)
-    emu = EmulatedRunner(steps, plan, lid, 8).run(data, off)
+    emu_runner = EmulatedRunner(steps, plan, lid, 8)
+    emu = emu_runner.run(data, off)
     assert res.dead is not None and emu.dead is not None
     assert np.count_nonzero(res.dead) > len(corpus) // 10
+    # neither side flags a document (both take the host's ICU marks; the language gate filters
+    # the mostly-CJK document, which gets none, before any segmentation): every document is compared
+    assert runner.dict_marks and emu_runner.dict_marks and any(host.has_dict_script(t) for t in corpus)
+    _assert_flags(res.flags, np.zeros(len(corpus)), corpus)
+    _assert_flags(emu.flags, np.zeros(len(corpus)), corpus)
     ok = (res.flags == 0) & (emu.flags == 0)
+    assert np.count_nonzero(ok) == len(corpus)
     diff = np.nonzero(ok & (res.dead != emu.dead))[0]
     assert len(diff) <= max(2, len(corpus) // 500), diff[:10]
 
@@ -258,11 +299,15 @@ def test_split_documents_match_host_emulation(host, corpus, runner_parts, monkey
     lens = np.diff(off)
     assert np.count_nonzero(lens > runner.split_doc_bytes) >= 20
     res = runner.run(data, off)
+    assert runner.dict_marks
+    _assert_flags(res.flags, np.zeros(n), corpus)
+    dict_v = _dict_docs(host, data, off)
     for s, idx in enumerate(plan.stages):
         if s not in runner.gr_split:
             continue
         ref, rflags = host.emulate_stage(steps, idx, np.ascontiguousarray(data), np.ascontiguousarray(off), 8,
                                          lid.native())
+        assert np.array_equal(rflags, np.where(dict_v, DOC_NEEDS_CPU, 0)), np.nonzero((rflags != 0) != dict_v)[0][:8]
         width_total, layout = runner.stage_layout[s]
         for (kind, width, prefix), step_i in zip(layout, idx):
             if kind != KIND_GOPHER_REP:
@@ -270,6 +315,7 @@ def test_split_documents_match_host_emulation(host, corpus, runner_parts, monkey
             p = runner.pass_of_step[step_i]
             live = ~((res.dead != 0) & (res.dead <= p)) if res.dead is not None else np.ones(n, bool)
             ok = (res.flags == 0) & (rflags == 0) & live
+            assert np.count_nonzero(ok) == n - np.count_nonzero(~live) - np.count_nonzero(dict_v & live)
             assert np.count_nonzero(ok & (lens > runner.split_doc_bytes)) >= 10  # split docs compared
             a = res.stage_recs[s][prefix * n:(prefix + width) * n].reshape(n, width)
             b = ref[prefix * n:(prefix + width) * n].reshape(n, width)
@@ -311,18 +357,30 @@ def test_pre_decoded_long_documents_match_host(host, runner_parts, monkeypatch):
     a, b = res["65536"], res["0"]
     np.testing.assert_array_equal(a.flags, b.flags)
     assert a.flags[10] != 0  # the dictionary-script document
+    # ... for the CPU path, not for an arena overflow, and no other document is flagged
+    assert not runner.dict_marks and [i for i, t in enumerate(texts) if host.has_dict_script(t)] == [10]
+    expected = np.zeros(n)
+    expected[10] = DOC_NEEDS_CPU
+    _assert_flags(a.flags, expected, texts)
     for s, idx in enumerate(plan.stages):
         ver = plan.stage_version[s]
         vd, vo = (data, off) if ver == 0 else a.versions[ver]
         np.testing.assert_array_equal(a.stage_recs[s], b.stage_recs[s])
         ref, rflags = host.emulate_stage(steps, idx, np.ascontiguousarray(vd), np.ascontiguousarray(vo), 8,
                                          lid.native())
+        dict_v = _dict_docs(host, vd, vo)
+        assert np.array_equal(rflags, np.where(dict_v, DOC_NEEDS_CPU, 0)), np.nonzero((rflags != 0) != dict_v)[0][:8]
         for (kind, width, prefix), step_i in zip(runner.stage_layout[s][1], idx):
             if kind == 4:
                 continue
             ok = (a.flags == 0) & (rflags == 0)
+            live = np.ones(n, bool)
             if a.dead is not None:
-                ok &= ~((a.dead != 0) & (a.dead <= runner.pass_of_step[step_i]))
+                live = ~((a.dead != 0) & (a.dead <= runner.pass_of_step[step_i]))
+                ok &= live
+            # floor: the documents left out are the gate-skipped ones and the dictionary-script one
+            gone = dict_v | (np.arange(n) == 10)
+            assert np.count_nonzero(ok) == n - np.count_nonzero(~live) - np.count_nonzero(gone & live)
             if ver == 0:
                 assert np.count_nonzero(ok & (lens >= 65536)) >= 2
             x = a.stage_recs[s][prefix * n:(prefix + width) * n].reshape(n, width)
