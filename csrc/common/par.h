@@ -1,6 +1,6 @@
 // Per-document parallel primitives.
 //
-// The document algorithms in docproc.h are written against this small interface so the same
+// The document algorithms (docproc.h: the map of their headers) are written against this small interface so the same
 // source runs as a wave64 kernel on the MI355X (WavePar: one wavefront per document, lanes
 // cooperate through DPP shuffles / ballots, no LDS needed) and sequentially on the host
 // (SeqPar: used to differential-test the device algorithms against the ICU oracle on CPU, and
@@ -22,7 +22,6 @@
 //  * single(f): f() runs once (lane 0).
 //  * cas64/min32/min64/add32/add64/max32/or32/fetch_or32: atomics on scratch memory.
 #pragma once
-#include "langid.h"
 #include "tb_common.h"
 
 // Chunks of 64 items whose loads a wave issues together in the latency-bound passes (WavePar).
@@ -537,11 +536,7 @@ struct BlockPar {
   static_assert(NT % 64 == 0 && NT >= 128 && NT <= 1024, "block of whole waves");
   static constexpr int NW = NT / 64;
   static constexpr bool kChunks = false;
-#ifdef TB_NO_PART_TABLES
-  static constexpr bool kPartTables = false;
-#else
   static constexpr bool kPartTables = true;   // long documents: LDS-partitioned hash tables
-#endif
   static constexpr uint32_t kWaves = NW;
   uint32_t tid, lane, wid;
   char* xs = nullptr;

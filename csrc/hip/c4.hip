@@ -4,6 +4,7 @@
 #include "kernel_common.h"
 
 #include "../common/badwords.h"
+#include "../common/c4_pass_a.h"
 
 namespace {
 

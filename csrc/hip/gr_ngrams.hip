@@ -2,6 +2,8 @@
 // exports (tb_gr_split_wave). (kernel_common.h: the families, the launch ABI.)
 #include "kernel_common.h"
 
+#include "../common/gopher_rep.h"
+
 namespace {
 
 // ---- n-gram orders of wave documents, one workgroup per document (k_gr_ngrams) ---------------

@@ -32,12 +32,14 @@
 // launch), DictIn / DictLines (devplan.h) -- and the launchers unpack them into the kernels'
 // argument lists. ops/kernels.py holds the one ctypes mirror of each.
 //
-// Only what more than one family uses lives here; the kernels of every unit sit in that unit's
-// anonymous namespace, and so do the device-side declarations below.
+// Only what more than one family uses lives here (of the document algorithms the context alone,
+// doc_ctx.h: each unit includes the family headers of csrc/common/ it calls, docproc.h has their
+// map); the kernels of every unit sit in that unit's anonymous namespace, and so do the
+// device-side declarations below.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "../common/docproc.h"
+#include "../common/doc_ctx.h"
 
 using namespace tb;
 

@@ -2,6 +2,13 @@
 // kernel. (kernel_common.h: the families, the launch ABI.)
 #include "kernel_common.h"
 
+#include "../common/langid.h"
+// doc_text.h: nothing here calls it. It defines a static __constant__ table (g_wb_pair_tab), and a
+// table defined in a header is emitted into every unit that includes it, read or not; the include
+// keeps this unit's code object what it was while every unit included all of docproc.h. Follow-up:
+// declare the table where it is read, then drop this include (180 bytes of .rodata go with it).
+#include "../common/doc_text.h"
+
 namespace {
 
 // index of the highest set bit of m (m != 0)

@@ -3,6 +3,9 @@
 // workgroups run. (kernel_common.h: the families, the launch ABI.)
 #include "kernel_common.h"
 
+#include "../common/doc_dedup.h"
+#include "../common/doc_text.h"
+
 namespace {
 
 __global__ void k_pow_table(uint64_t* pw, uint32_t n) {

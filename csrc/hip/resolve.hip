@@ -4,6 +4,11 @@
 
 #include "../common/gate.h"
 #include "../common/metafmt.h"
+// doc_text.h: nothing here calls it. It defines a static __constant__ table (g_wb_pair_tab), and a
+// table defined in a header is emitted into every unit that includes it, read or not; the include
+// keeps this unit's code object what it was while every unit included all of docproc.h. Follow-up:
+// declare the table where it is read, then drop this include (180 bytes of .rodata go with it).
+#include "../common/doc_text.h"
 
 namespace {
 

@@ -6,6 +6,8 @@
 
 #include "kernel_common.h"
 
+#include "../common/stage_analyze.h"
+
 namespace {
 
 // The stage kernel is register-bound (occupancy = waves/SIMD the VGPR budget allows). With the

@@ -58,7 +58,7 @@ void emulate_stage(const std::vector<StepCfg>& steps, const std::vector<int>& id
 // split_tasks > 0: every document runs the intra-document split of its GopherRepetition step
 // (stage export, then the k_gr_dup_split tasks in turn, each in its slice of the arena rest)
 uint64_t line_stats_buffer_words(const int64_t* off, int64_t ndocs);  // u32 size of a batch's line export
-// line_stats: the C4 line export of the batch (docproc.h line_stats_base layout), written by
+// line_stats: the C4 line export of the batch (doc_ctx.h line_stats_base layout), written by
 // emulate_stage and read by emulate_c4 of the same content version, as on the device
 void emulate_c4(const StepCfg& step, int64_t ndocs, const char* data, const int64_t* off, int nthreads,
                 std::vector<int64_t>& rec, std::string& new_data, std::vector<int64_t>& new_off,

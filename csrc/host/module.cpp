@@ -909,7 +909,7 @@ PYBIND11_MODULE(_tbhost, m) {
      py::arg("dict_moff") = py::none(), py::arg("dict_bits") = py::none(), py::arg("dict_words") = py::none());
   m.def("line_stats_words", [](py::array_t<int64_t, py::array::c_style> off) {
     return line_stats_buffer_words(off.data(), (int64_t)off.size() - 1);
-  }, "u32 words of a batch's C4 line export buffer (docproc.h line_stats_base)");
+  }, "u32 words of a batch's C4 line export buffer (doc_ctx.h line_stats_base)");
   m.def("gate_host", [](const py::bytes& gate, const std::vector<py::array_t<int64_t, py::array::c_style>>& recs,
                         int64_t ndocs, py::array_t<uint32_t, py::array::c_style> flags,
                         py::array_t<uint8_t, py::array::c_style> dead, int code) {

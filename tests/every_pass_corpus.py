@@ -54,7 +54,7 @@ def nbytes(text):
     return len(text.encode())
 
 
-DOC_NEEDS_CPU = 1  # docproc.h
+DOC_NEEDS_CPU = 1  # doc_ctx.h
 
 
 def expected_flags(h, texts, dict_marks, segments=True):

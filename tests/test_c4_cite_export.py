@@ -1,4 +1,4 @@
-"""C4 pass A's citation path from the stage's line export (docproc.h c4_pass_a_cite_export): the
+"""C4 pass A's citation path from the stage's line export (c4_pass_a.h c4_pass_a_cite_export): the
 host emulation of the device algorithms against the CPU ICU oracle on documents dense in
 citation shapes (reference CITATION_REGEX, c4_filters.rs:33): multi-number lists, spaces inside
 the brackets, citations glued to words, a trailing comma, a line feed inside a list, Arabic-Indic

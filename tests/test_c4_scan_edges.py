@@ -1,4 +1,4 @@
-"""C4 pass A's byte scan (docproc.h c4_byte_scan, c4_phrases_at: phrases matched from packed bytes)
+"""C4 pass A's byte scan (c4_pass_a.h c4_byte_scan, c4_phrases_at: phrases matched from packed bytes)
 and the stop-word fast path (is_stop_word) inside whole runs: the texts of
 tools/c4_scan_selftest.cpp and documents built around them (tests/c4_scan_corpus.py) through the
 host emulation of the device algorithms and through the CPU ICU oracle. Status, first failing step,

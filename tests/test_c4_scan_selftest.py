@@ -1,6 +1,6 @@
 """C4 pass A's byte scan and the stop-word fast path under sanitizers: tools/c4_scan_selftest.cpp
-(csrc/common/docproc.h c4_byte_scan / c4_phrases_at / is_stop_word on the host, over phrases at
-every alignment, cut by the end of the text and across the scan's item boundaries, in buffers that
+(csrc/common/c4_pass_a.h c4_byte_scan / c4_phrases_at and stage_analyze.h is_stop_word on the
+host, over phrases at every alignment, cut by the end of the text and across the scan's item boundaries, in buffers that
 end with the text, against ci_contains / ci_starts_with and a std::set of stop words) built with
 AddressSanitizer + UBSan as a stand-alone program. Host code only (GPU sanitizers are not
 available on the MI355X pool)."""

@@ -202,7 +202,7 @@ def test_split_tasks_equal_one_pass_and_fit_the_reservation(host):
             assert one <= host.SCRATCH_PER_BYTE and split <= host.SCRATCH_PER_BYTE_SPLIT, (one, split)
     finally:
         host.set_scratch_probe(False)
-    # under the real reservation nothing overflows (DOC_OVERFLOW = 2, docproc.h -> CPU path)
+    # under the real reservation nothing overflows (DOC_OVERFLOW = 2, doc_ctx.h -> CPU path)
     for idx in plan.stages:
         _, f = host.emulate_stage(steps, idx, data, off, 4, lid, 0, split_tasks=tasks)
         assert not (f & 2).any()

@@ -24,7 +24,7 @@ from textblaster_amd.pipeline.engine import Engine  # noqa: E402
 from textblaster_amd.utils import synth  # noqa: E402
 
 CFG = os.path.join(REPO, "config", "bench_pipeline.yaml")
-DOC_OVERFLOW = 2  # docproc.h
+DOC_OVERFLOW = 2  # doc_ctx.h
 TUNE_OFF = "gate=0"
 TUNE_PRE = "gate=0,pre_doc_bytes=65536"
 

@@ -40,7 +40,7 @@ def corpus():
     return kernels_corpus()
 
 
-DOC_NEEDS_CPU, DOC_OVERFLOW = 1, 2  # docproc.h
+DOC_NEEDS_CPU, DOC_OVERFLOW = 1, 2  # doc_ctx.h
 
 
 def _dict_docs(host, vd, vo):

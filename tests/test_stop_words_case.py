@@ -1,7 +1,7 @@
 """GopherQualityFilter stop words with mixed-case and non-ASCII config entries (reference
 gopher_quality.rs: ``stop_words.contains(&w.to_lowercase())`` against the raw entries). The device
 code has two lookups — an ASCII fast table for words of <= 7 bytes and the hashed lowercase-bytes
-table (csrc/common/docproc.h is_stop_word) — and both must follow that rule: a capitalised entry
+table (csrc/common/stage_analyze.h is_stop_word) — and both must follow that rule: a capitalised entry
 ("The") never matches, since no lowercased word is capitalised; "I" matches the entry "i";
 "Über" / "NAÏVE" match "über" / "naïve" through the slow path. The emulated device path must equal
 the CPU ICU oracle, and the counts are pinned."""

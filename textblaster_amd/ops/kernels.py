@@ -152,7 +152,7 @@ _SIGS = {
 }
 
 
-# docproc.h PreDoc (checked against tb_sizeof_pre_doc)
+# doc_ctx.h PreDoc (checked against tb_sizeof_pre_doc)
 PRE_DOC = np.dtype([("off", "<u8"), ("prop", "<u8"), ("wbm", "<u8"), ("nl_pos", "<u8"), ("nl_len", "<u8"),
                     ("n", "<u4"), ("C", "<u4"), ("dict", "<u4"), ("NL", "<u4"), ("tcs", "<u4"), ("tce", "<u4"),
                     ("nl_a", "<u4"), ("nl_e", "<u4"), ("wtmp", "<u8"), ("wcs", "<u8"), ("wce", "<u8"),
@@ -285,7 +285,7 @@ class Kernels:
     def stage_analyze(self, plan, stage, docs: Docs, work: Work, tables: Tables, line_stats=None, gr_export=None,
                       dict_in: Optional[DictIn] = None):
         """k_stage_analyze_wave over launch positions [0, docs.n_launch) (0: all); ``line_stats``
-        (uint32, >= 4 * (total bytes / 8 + 16 ndocs) + 16): the C4 line export (docproc.h
+        (uint32, >= 4 * (total bytes / 8 + 16 ndocs) + 16): the C4 line export (stage_analyze.h
         StageOut::line_stats), document d at 4 * (off[d] / 8 + 16 d). ``gr_export`` (zeroed, >=
         n_launch descriptors): split mode, every launched document exports its word arrays and
         gr_split_wave finishes its n-gram orders (the launcher then runs k_stage_analyze_wave_ex,

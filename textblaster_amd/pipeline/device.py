@@ -397,7 +397,7 @@ KIND_FINEWEB = 3
 
 
 def line_stats_stages(plan: ExecPlan, stage_layout, tune: Optional[DeviceTuning] = None) -> Dict[int, int]:
-    """C4 line export (docproc.h export_line_stats): per content version read by a C4 pass, the
+    """C4 line export (stage_analyze.h export_line_stats): per content version read by a C4 pass, the
     first stage of that version that segments words and Rust lines (GopherQuality / FineWeb);
     it exports every line's trimmed span, word count and longest word, and the C4 pass reads them
     instead of decoding and segmenting the text again. TB_TUNE c4_line_stats=0 turns it off."""
@@ -927,7 +927,7 @@ class DeviceRunner:
         for ver in range(self.plan.n_versions):
             main.wait_event(b.ready[ver])
             # uint32 [4 * (bytes / 8 + 16 * documents) + 16]: document d's region at
-            # 4 * (off[d] / 8 + 16 d) (docproc.h line_stats_base)
+            # 4 * (off[d] / 8 + 16 d) (doc_ctx.h line_stats_base)
             b.lstats = None
             if ver in self.line_stats_stage:
                 b.lstats = rt.empty(4 * (b.versions[ver][2] // 8 + 16 * b.ndocs) + 16, np.uint32)

@@ -33,7 +33,7 @@ from .plan import ExecPlan, build_plan
 from . import tuning
 from .tuning import DeviceTuning
 
-# per-document device flag bits (csrc/common/docproc.h DocFlag)
+# per-document device flag bits (csrc/common/doc_ctx.h DOC_*)
 DOC_NEEDS_CPU = 1
 DOC_OVERFLOW = 2
 

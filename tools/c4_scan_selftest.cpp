@@ -1,5 +1,5 @@
-// Stand-alone self-test of C4 pass A's byte scan and of the stop-word fast path (csrc/common/docproc.h
-// on the host), built with AddressSanitizer + UndefinedBehaviorSanitizer by
+// Stand-alone self-test of C4 pass A's byte scan and of the stop-word fast path (csrc/common/c4_pass_a.h
+// and stage_analyze.h on the host), built with AddressSanitizer + UndefinedBehaviorSanitizer by
 // tests/test_c4_scan_selftest.py:
 //
 //   * c4_byte_scan's bits against ci_contains per phrase over the whole text and the per-byte
@@ -19,7 +19,8 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/common/docproc.h"
+#include "../csrc/common/c4_pass_a.h"
+#include "../csrc/common/stage_analyze.h"
 
 using namespace tb;
 
